@@ -9,7 +9,11 @@ per prompt.  After the K timed steps every prompt's K codec frames are decoded t
 decoder inside the same timed region.  value = audio-seconds produced by all ranks / wall seconds
 (RTF^-1) of AR + DAC; the AR-only and DAC-only rates are reported beside it.
 
-Beside the headline line's fields, three more legs of BASELINE.json's configs run on the same GPU:
+A plain run does that and nothing else: set up, warm up, the K timed steps, the result line (and with
+--dump-outputs DIR the tokens and PCM the timed steps returned, as .npy files).  Everything below runs
+only with --full, which fills the line's other fields: the GEMV / attention roofline and copy peak, the
+other Parler shapes (8 prompts per GPU, sampled, prompt passes, generate(), one prompt per runner), the
+CPU baseline, and three more legs of BASELINE.json's configs on the same GPU:
 "kokoro" (configs[1], Kokoro-82M fp16 end to end: durations, decoder, iSTFTNet vocoder), "dia" (configs[3], Dia-1.6B Q8_0 CFG
 decode) and "orpheus" (configs[4]'s per-GPU shard, Orpheus-3B Q4_K decode), each with its own rate; the orpheus leg carries the dequant-GEMV
 roofline at the sizes where the matrix-core GEMV streams (every Orpheus matrix is >= 4 MiB).
@@ -186,6 +190,24 @@ def gather_audio(dist, rank, world, local, pcms):
         offs = np.cumsum([0] + n)
         out += [host[offs[i]:offs[i + 1]] for i in range(len(n))]
     return out
+
+
+DUMP_PCM_SAMPLES = 12 << 20  # float32 samples of PCM kept by --dump-outputs (48 MiB; the tokens are a few MiB)
+
+
+def dump_outputs(path, toks, pcms):
+    """--dump-outputs: what a caller of the timed steps receives, as float32 .npy files -- codec_tokens
+    [prompts, steps, heads] (the greedy ids, exact in float32) and, with the DAC leg, pcm: every prompt's
+    samples end to end in prompt order, or when those are more than DUMP_PCM_SAMPLES a fixed sample of
+    them (the same seeded positions for the same shape, ascending)."""
+    out = pathlib.Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "codec_tokens.npy", np.ascontiguousarray(toks, dtype=np.float32))
+    if pcms is not None:
+        flat = np.concatenate([np.asarray(p, dtype=np.float32).reshape(-1) for p in pcms])
+        if flat.size > DUMP_PCM_SAMPLES:
+            flat = flat[np.sort(np.random.default_rng(0).choice(flat.size, DUMP_PCM_SAMPLES, replace=False))]
+        np.save(out / "pcm.npy", flat)
 
 
 def cpu_baseline(args, n_threads, B):
@@ -747,7 +769,17 @@ def main():
     ap.add_argument("--orpheus-steps", type=int, default=64, help="timed Orpheus-3B decode steps per GPU (0 = skip)")
     ap.add_argument("--orpheus-batch", type=int, default=8, help="Orpheus prompts per GPU (64-prompt batch / 8 GPUs)")
     ap.add_argument("--dia-steps", type=int, default=64, help="timed Dia-1.6B decoder steps per GPU (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="beside the headline, every other leg and figure: the GEMV / attention "
+                    "roofline and copy peak, the 8-prompt, sampled, prompt-pass, generate()-shape and B=1 Parler legs, the "
+                    "Kokoro, Orpheus and Dia legs and the CPU baseline (their own options select among them; without --full "
+                    "none of them runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what they returned "
+                    "(every prompt's codec tokens and PCM) as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, the timed steps, the result line
+        args.no_cpu_baseline = True
+        args.p8 = args.sampled_steps = args.prompt_pass = args.b1_replicas = 0
+        args.kokoro_prompts = args.orpheus_steps = args.dia_steps = 0
 
     rank, world, local, dist = dist_init()
     R = args.replicas
@@ -839,23 +871,27 @@ def main():
     dt = max_over_ranks(dist, local, t2 - t0)
     dt_ar = max_over_ranks(dist, local, t1 - t0)
     dt_dac = max_over_ranks(dist, local, t2 - t1)
-    gather_tokens(dist, rank, world, local, toks)
+    all_toks = gather_tokens(dist, rank, world, local, toks)
     # the one data exchange of the sharded job: every prompt's audio to rank 0
     gathered = None
     if dac is not None:
         tg0 = time.perf_counter()
         gathered = gather_audio(dist, rank, world, local, pcm)
         t_gather = time.perf_counter() - tg0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, all_toks, gathered)
     total_prompts = per_gpu * world
     audio_s = total_prompts * args.steps * SAMPLES_PER_STEP / SAMPLE_RATE
-    roof = gemv_roofline(be, runner, max(5, min(40, args.steps // 5)))
-    try:
-        cp = copy_peak(be)  # streaming-copy rate of this GPU (read + write), beside the spec peak
-        roof["measured_copy_peak_gbs"] = cp["kernel"]
-        roof["measured_copy_runtime_gbs"] = cp["runtime"]
-    except Exception as e:  # noqa: BLE001  (a measurement beside the line, never a reason to lose it)
-        roof["measured_copy_peak_gbs"] = None
-        print(f"bench: copy peak failed: {e!r}", file=sys.stderr, flush=True)
+    roof = None
+    if args.full:
+        roof = gemv_roofline(be, runner, max(5, min(40, args.steps // 5)))
+        try:
+            cp = copy_peak(be)  # streaming-copy rate of this GPU (read + write), beside the spec peak
+            roof["measured_copy_peak_gbs"] = cp["kernel"]
+            roof["measured_copy_runtime_gbs"] = cp["runtime"]
+        except Exception as e:  # noqa: BLE001  (a measurement beside the line, never a reason to lose it)
+            roof["measured_copy_peak_gbs"] = None
+            print(f"bench: copy peak failed: {e!r}", file=sys.stderr, flush=True)
     graph_nodes = runner.last_graph_nodes()
     dac_nodes = dac.last_graph_nodes() if dac is not None else None
     for xb, rd in dac_workers[R:]:

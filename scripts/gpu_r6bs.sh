@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out
 for i in 1 2 3; do
   for v in poll block; do
     if [ $v = block ]; then export TTS_HIP_BLOCKING_SYNC=1; else unset TTS_HIP_BLOCKING_SYNC; fi
-    timeout -k 10 400 python -u bench.py --steps 10 --warmup 3 --no-dac --kokoro-prompts 0 --orpheus-steps 0 --dia-steps 0 --p8 0 \
+    timeout -k 10 400 python -u bench.py --full --steps 10 --warmup 3 --no-dac --kokoro-prompts 0 --orpheus-steps 0 --dia-steps 0 --p8 0 \
       --sampled-steps 0 --prompt-pass 0 --no-cpu-baseline --no-prefill --b1-steps 60 > gpurun_out/r6bs_${v}_$i.json 2> gpurun_out/r6bs_${v}_$i.err
     rc=$?; echo "$v $i rc $rc"; [ $rc -eq 0 ] || exit $rc
     python3 -c "

@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 timeout -k 10 300 python -u -m pytest tests/test_gemv_gpu.py tests/test_parler_gpu.py -k "column_pairs or many_prompt" -x -q --timeout 200 --timeout-method thread > gpurun_out/r6e_tests.log 2>&1
 rc=$?; echo "tests rc $rc"; tail -3 gpurun_out/r6e_tests.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python -u bench.py --steps 5 --warmup 3 --no-dac --kokoro-prompts 0 --orpheus-steps 0 --dia-steps 0 --p8 0 \
+timeout -k 10 400 python -u bench.py --full --steps 5 --warmup 3 --no-dac --kokoro-prompts 0 --orpheus-steps 0 --dia-steps 0 --p8 0 \
   --sampled-steps 0 --prompt-pass 0 --no-cpu-baseline --no-prefill --b1-steps 60 > gpurun_out/r6e_b1.json 2> gpurun_out/r6e_b1.err
 rc=$?; echo "b1 rc $rc"; python3 -c "
 import json;d=json.loads(open('gpurun_out/r6e_b1.json').read().splitlines()[-1]);b=d['parler_b1']

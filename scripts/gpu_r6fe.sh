@@ -9,7 +9,7 @@ rc=$?; tail -3 gpurun_out/r6fe_tests.log; [ $rc -eq 0 ] || exit $rc
 for i in 1 2 3; do
   for v in skip all; do
     if [ $v = all ]; then export TTS_CO_FENCE_ALL=1; else unset TTS_CO_FENCE_ALL; fi
-    timeout -k 10 400 python -u bench.py --steps 5 --warmup 3 --no-dac --kokoro-prompts 0 --orpheus-steps 0 --dia-steps 0 --p8 0 \
+    timeout -k 10 400 python -u bench.py --full --steps 5 --warmup 3 --no-dac --kokoro-prompts 0 --orpheus-steps 0 --dia-steps 0 --p8 0 \
       --sampled-steps 0 --prompt-pass 0 --no-cpu-baseline --no-prefill --b1-steps 60 > gpurun_out/r6fe_${v}_$i.json 2> gpurun_out/r6fe_${v}_$i.err
     rc=$?; echo "$v $i rc $rc"; [ $rc -eq 0 ] || exit $rc
     python3 -c "

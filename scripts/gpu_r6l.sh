@@ -9,7 +9,7 @@ timeout -k 10 300 python3 -u -m pytest -x -q --timeout 120 --timeout-method thre
 rc=$?; tail -3 gpurun_out/r6l_tests.log; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 400 python3 -u scripts/ab_ar.py --blocks 5 --steps 12 base=GEMM_KR_XCD:0 xcd=GEMM_KR_XCD:1 > gpurun_out/r6l_ab.log 2>&1
 rc=$?; cat gpurun_out/r6l_ab.log | grep variant; [ $rc -eq 0 ] || exit $rc
-B="python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-dac --graphs 0 --no-prefill --ctx 448 --kokoro-prompts 0 --orpheus-steps 0 --dia-steps 0 --b1-replicas 0 --p8 0 --sampled-steps 0 --prompt-pass 0 --gemm-kr-xcd 1"
+B="python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-dac --graphs 0 --no-prefill --ctx 448 --kokoro-prompts 0 --orpheus-steps 0 --dia-steps 0 --b1-replicas 0 --p8 0 --sampled-steps 0 --prompt-pass 0 --gemm-kr-xcd 1"
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --stats -d gpurun_out/pmc6x_fetch -o run --output-format csv -- $B > gpurun_out/pmc6x_fetch.log 2>&1 &&
 timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --stats -d gpurun_out/pmc6x_write -o run --output-format csv -- $B > gpurun_out/pmc6x_write.log 2>&1
 rc=$?; echo "pmc rc $rc"; tail -2 gpurun_out/pmc6x_fetch.log

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/study
 mkdir -p "$O"
 cd "$R"
-AR="--no-dac --kokoro-prompts 0 --orpheus-steps 0 --dia-steps 0 --no-cpu-baseline --b1-replicas 0 --steps 200"
+AR="--full --no-dac --kokoro-prompts 0 --orpheus-steps 0 --dia-steps 0 --no-cpu-baseline --b1-replicas 0 --steps 200"
 T="-x -v --timeout 300 --timeout-method thread"
 ar_line() {  # bench.py AR-only line: ms/step, audio-s/s, average GEMV launch, prefill ms per replica
   python3 -c "import json,sys;d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]);print(sys.argv[2], d['ar_ms_per_step'], d['ar_audio_sec_per_s'], d['roofline']['avg_launch_us'], d.get('prefill_ms', {}).get('per_replica'))" "$1" "$2"
@@ -65,7 +65,7 @@ case "$1" in
     f=$(find "$O/proft" -name "*kernel_trace.csv" | sort | tail -1) && python3 scripts/step_breakdown.py "$f" 5 30 > "$O/ar_breakdown.txt" && cat "$O/ar_breakdown.txt" | cut -c1-150 ;;
   orph_trace)  # kernel trace of the Orpheus leg + per-step breakdown (markers: the wide-vocabulary greedy step)
     shift
-    (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace -d "$O/profo" -o run --output-format csv -- python3 "$R/bench.py" --steps 1 --warmup 1 --no-dac --kokoro-prompts 0 --dia-steps 0 --no-cpu-baseline --b1-replicas 0 --orpheus-steps 40 "$@" > "$O/orph_trace.log" 2>&1) &&
+    (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace -d "$O/profo" -o run --output-format csv -- python3 "$R/bench.py" --full --steps 1 --warmup 1 --no-dac --kokoro-prompts 0 --dia-steps 0 --no-cpu-baseline --b1-replicas 0 --orpheus-steps 40 "$@" > "$O/orph_trace.log" 2>&1) &&
     f=$(find "$O/profo" -name "*kernel_trace.csv" | sort | tail -1) && python3 scripts/step_breakdown.py "$f" 10 25 - k_greedy_step_wide > "$O/orph_breakdown.txt" && cut -c1-150 "$O/orph_breakdown.txt" ;;
   attn_opts)   # split-attention geometry (scores positions per workgroup x P.V dims per workgroup), AR-only
     for cfg in "--attn-ks 2 --attn-pv8 0" "--attn-ks 1 --attn-pv8 0" "--attn-ks 2 --attn-pv8 1" "--attn-ks 1 --attn-pv8 1" "--attn-ks 4 --attn-pv8 0" "--attn-ks 2 --attn-pv8 0"; do
@@ -76,7 +76,7 @@ case "$1" in
     shift
     for cfg in "$@"; do
       n=$(echo $cfg | tr -d ' -')
-      timeout -k 10 300 python3 bench.py --steps 1 --warmup 1 --no-dac --kokoro-prompts 0 --orpheus-steps 0 --no-cpu-baseline --b1-replicas 0 --dia-steps 100 $cfg > "$O/dia_$n.log" 2>&1 &&
+      timeout -k 10 300 python3 bench.py --full --steps 1 --warmup 1 --no-dac --kokoro-prompts 0 --orpheus-steps 0 --no-cpu-baseline --b1-replicas 0 --dia-steps 100 $cfg > "$O/dia_$n.log" 2>&1 &&
       python3 -c "import json,sys;d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])['dia'];print(sys.argv[2], d['ms_per_step'], d['encoder_step_ms'])" "$O/dia_$n.log" "$cfg" || exit 1
     done ;;
   dac20_trace)  # kernel trace of the driver's short line (AR + DAC of 20 frames), AR/DAC legs only
@@ -85,7 +85,7 @@ case "$1" in
     tail -1 "$O/dac20_trace.log" | cut -c1-300 ;;
   dia_trace)   # kernel trace of the Dia leg + per-step breakdown (markers: the greedy step)
     shift
-    (cd /tmp && export TMPDIR=/tmp DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 && timeout -k 10 300 rocprofv3 --kernel-trace -d "$O/profdia" -o run --output-format csv -- python3 "$R/bench.py" --steps 1 --warmup 1 --no-dac --kokoro-prompts 0 --orpheus-steps 0 --no-cpu-baseline --b1-replicas 0 --dia-steps 40 "$@" > "$O/dia_trace.log" 2>&1) &&
+    (cd /tmp && export TMPDIR=/tmp DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 && timeout -k 10 300 rocprofv3 --kernel-trace -d "$O/profdia" -o run --output-format csv -- python3 "$R/bench.py" --full --steps 1 --warmup 1 --no-dac --kokoro-prompts 0 --orpheus-steps 0 --no-cpu-baseline --b1-replicas 0 --dia-steps 40 "$@" > "$O/dia_trace.log" 2>&1) &&
     f=$(find "$O/profdia" -name "*kernel_trace.csv" | sort | tail -1) && python3 scripts/step_breakdown.py "$f" 3 25 - k_greedy_step > "$O/dia_breakdown.txt" && cut -c1-150 "$O/dia_breakdown.txt" ;;
   tests)       # selected GPU test files, e.g. scripts/gpu_study.sh tests tests/test_dia_gpu.py
     shift

@@ -5,7 +5,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/tracer20; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 export TTS_HIP_CRASH_HANDLER=1 DEBUG_CLR_GRAPH_PACKET_CAPTURE=0
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/run -o run --output-format csv -- python3 $R/bench.py --steps 20 --warmup 5 \
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/run -o run --output-format csv -- python3 $R/bench.py --full --steps 20 --warmup 5 \
   --no-cpu-baseline --b1-wide 0 --sampled-steps 0 $TRACER_EXTRA > $O/run.log 2>&1
 rc=$?
 echo "tracer bench20 (packet capture off) rc $rc"

@@ -57,7 +57,7 @@ def main():
     pat = sys.argv[4] if len(sys.argv) > 4 else "k_gemv_q4_K"
     last = int(sys.argv[5]) if len(sys.argv) > 5 else sampled_launches(fdir.rstrip("/") + ".log")
     cmd = sys.argv[6] if len(sys.argv) > 6 else (
-        "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE --kernel-trace --stats -- python3 bench.py --steps 10 "
+        "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE --kernel-trace --stats -- python3 bench.py --full --steps 10 "
         "--warmup 2 --no-cpu-baseline --no-dac --graphs 0 --ctx 16 (decode dispatches only)")
     f, nf, fs = per_kernel(fdir, "FETCH_SIZE", pat, last)
     w, nw, ws = per_kernel(wdir, "WRITE_SIZE", pat, last)

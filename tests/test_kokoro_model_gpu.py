@@ -54,3 +54,28 @@ def test_kokoro_model_matches_oracle(hip, name, n, seed, wtype):
     finally:
         g.close()
         o.close()
+
+
+@pytest.mark.gpu
+def test_kokoro_durations_every_pass_identical(hip):
+    """The duration graph at 82M widths (F32) many times over on one runner: every pass equals the
+    oracle's bit for bit.  A GEMV that read the source of a skipped CONT after the allocator had handed
+    that memory to the product's output came out wrong in about 7 passes of 1000 (workgroups racing);
+    400 passes would have met that with probability 0.94, and a correct executor never fails this."""
+    cfg = ttship.kokoro_config(**dict(CFGS["kokoro82m"], weight_type=ttship.F32))
+    toks = tokens(6, 2)
+    o = ttship.Kokoro(py_oracle.iface(16), cfg)
+    try:
+        ho, lo = o.durations(toks)
+    finally:
+        o.close()
+    g = ttship.Kokoro(hip.iface(), cfg)
+    try:
+        bad = []
+        for rep in range(400):
+            hg, lg = g.durations(toks)
+            if not (np.array_equal(hg, ho) and np.array_equal(lg, lo)):
+                bad.append((rep, float(np.max(np.abs(hg - ho)))))
+        assert not bad, f"{len(bad)} of 400 passes differ from the oracle: {bad[:5]}"
+    finally:
+        g.close()

@@ -730,7 +730,9 @@ struct Planner {
         if ((mask & TTS_FUSE_CONTREAD) && x->op == TTS_OP_CONT && index.count(x) && act[index[x]] == 0 && uses[x] == 1 &&
             next_real(index[x]) == i && x->src[0] && !(x->flags & (TTS_FLAG_OUTPUT | TTS_FLAG_PERSIST))) {
             const tts_tensor * s0 = x->src[0];
-            if (s0->type == TTS_TYPE_F32 && contiguous(s0) && contiguous(x) && nel(s0) == nel(x)) {  // the same bytes
+            // the copy's source is dead after the copy, so the allocator may have handed its memory to the
+            // product: every workgroup reads all of src1 while others write their rows, so no overlap at all
+            if (s0->type == TTS_TYPE_F32 && contiguous(s0) && contiguous(x) && nel(s0) == nel(x) && !overlap(mm0, s0)) {  // the same bytes
                 it.xsrc = s0;
                 act[index[x]] = -1;
             }
@@ -872,7 +874,7 @@ struct Planner {
                     it.epi = EPI_ADD;
                     it.res = E->src[1];
                 }
-                if (it.epi != EPI_NONE && (a0->type != TTS_TYPE_F32 || !overlap(E, x))) {
+                if (it.epi != EPI_NONE && (a0->type != TTS_TYPE_F32 || !overlap(E, x)) && !(it.xsrc && overlap(E, it.xsrc))) {
                     it.tgt[0] = GemvTarget{(float *)E->data, (int64_t)(E->ne[0]), 1};  // contiguous: column stride ne0
                     it.tgt[0].yt = E;
                     act[index[E]] = -1;

@@ -345,6 +345,10 @@ enum tts_hip_option {
                                      prefill GEMM: a wave per two 16-row tiles of one 16-column tile over the whole row, ggml's
                                      block chain in registers (no relay); 0 = the K-relay GEMM for every column count */
     TTS_HIP_OPT_GEMM_PF_NW = 42,  /* waves per prefill-GEMM workgroup: 4 (default; 8 row tiles share one operand copy) or 8 (16) */
+    TTS_HIP_OPT_ATTN_ONE = 43,    /* many-prompt decode attention (hd 64) where the four-wave all-dims P.V would run: 1 (default) = ONE launch,
+                                     a 256-thread workgroup per (head, query, sequence) that keeps the scores in LDS (k_attn_one: the
+                                     split pair's sums in its order, bit-identical), two rounds of 128 key positions in flight;
+                                     2 = rounds of 256 positions; 0 = the split pair (k_attn_scores + k_attn_pv_mp) */
     TTS_HIP_OPT_COALESCE = 37,    /* 1 (default): while the process-wide coalescer is on (tts_hip_coalesce_enable), this
                                      backend's graph_compute of a one-prompt decode step may join the same step of other
                                      backends on the device as one coalesced launch (tts_hip_coalesce_stats); 0 = never */
@@ -363,6 +367,15 @@ enum tts_fuse_bits {
                                 rope): that node reads the source and the copy is never made */
 };
 int tts_hip_set_option(tts_hip_backend_t backend, int option, int value);
+/* One decode attention launched directly, with the kernel choice of a graph's fused attention item (tests and
+ * micro-benchmarks; stream-ordered).  q [hd, n, H, B], k [hd, P, Hk, Bk] and v [P, hd, Hv, Bv] are f32 views of device
+ * memory (only data, ne and nb are read); mask is [n][P] f32 per sequence (mbs floats apart, 0 = shared) or NULL;
+ * out is [hd, H, n, B] contiguous, out2 an optional second copy.  koff / voff / moff / pseq (device arrays of B entries,
+ * all or none): sequence b's K / V byte offsets from k->data / v->data (the views' nb[3] is then ignored), its mask
+ * offset in floats and its key count (1 .. P), as a coalesced step of runners at different KV lengths launches it. */
+int tts_hip_attn_decode(tts_hip_backend_t backend, const tts_tensor * q, const tts_tensor * k, const tts_tensor * v,
+                        const float * mask, int64_t mbs, float scale, float * out, float * out2, const int64_t * koff,
+                        const int64_t * voff, const int64_t * moff, const int32_t * pseq);
 /* Step coalescer counters of `device` since process start: out[0] coalesced launches, [1] member steps they
  * carried, [2] steps a member ran alone after waiting, [3] groups refused (no coalesced form / mismatched
  * members), [4] the largest group, [5] host microseconds spent waiting for members, [6] coalesced launches whose

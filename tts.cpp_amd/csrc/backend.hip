@@ -802,6 +802,10 @@ extern "C" int tts_hip_set_option(tts_hip_backend_t be, int option, int value) {
         case TTS_HIP_OPT_GEMM_KR_CT2: be->gemm_kr_ct2 = value != 0; return 0;
         case TTS_HIP_OPT_GEMM_KR_INKERNEL: be->gemm_kr_ink = value < 0 ? 0 : value; return 0;
         case TTS_HIP_OPT_ATTN_PV_MP: be->attn_pv_mp = value == 2 ? 2 : value != 0; return 0;
+        case TTS_HIP_OPT_ATTN_ONE:
+            if (value < 0 || value > 2) return TTS_STATUS_BAD_ARG;
+            be->attn_one = value;
+            return 0;
         case TTS_HIP_OPT_GEMM_KR_NW: be->gemm_kr_nw = value == 8 ? 8 : 4; return 0;
         case TTS_HIP_OPT_GEMM_Q8: be->gemm_q8 = value != 0; return 0;
         case TTS_HIP_OPT_CU_PARTITION: {

@@ -209,6 +209,7 @@ void copy_options(tts_hip_backend * d, const tts_hip_backend * s) {
     d->attn_split_minp = s->attn_split_minp;
     d->attn_ks = s->attn_ks;
     d->attn_pv_mp = s->attn_pv_mp;
+    d->attn_one = s->attn_one;
     d->attn_pv8 = s->attn_pv8;
     d->attn_pv_uv16 = s->attn_pv_uv16;
     d->attn_fused_minp = s->attn_fused_minp;

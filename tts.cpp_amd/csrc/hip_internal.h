@@ -376,6 +376,7 @@ struct tts_hip_backend {
     int attn_split_minp = 128;
     int attn_ks = 2;   // split scores: 128 * attn_ks positions per workgroup (TTS_HIP_OPT_ATTN_KS)
     int attn_pv_mp = 1;  // split P.V: every dim of a (head, query, sequence) in one workgroup (TTS_HIP_OPT_ATTN_PV_MP)
+    int attn_one = 1;  // the one-launch 256-thread decode attention where k_attn_pv_mp<8, 4, 4> would run (TTS_HIP_OPT_ATTN_ONE)
     int attn_pv8 = 0;  // split P.V: 8 output dims per workgroup instead of 16 (TTS_HIP_OPT_ATTN_PV8)
     int attn_pv_uv16 = 0;  // split P.V: one 16-chunk V batch per lane for P <= 1024 (TTS_HIP_OPT_ATTN_PV16; measured equal, off)
     int attn_fused_minp = 0;  // the one-launch 1024-thread decode attention from this many keys (0 = off: measured no faster in the Parler step)

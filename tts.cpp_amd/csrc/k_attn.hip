@@ -669,6 +669,196 @@ __global__ __launch_bounds__(64 * NW) void k_attn_pv_mp(AttnArgs a, const float 
 }
 
 // ------------------------------------------------------------------------------------------
+// One-launch decode attention for the many-prompt shape (hd 64; TTS_HIP_OPT_ATTN_ONE): the split pair
+// k_attn_scores + k_attn_pv_mp<8, 4, 4> in ONE 256-thread workgroup per (head, query, sequence) -- the
+// k_attn_pv_mp grid.  At 32 lock-step prompts the pair is held by its fixed costs, not by bandwidth: two
+// launch ramps, and the scores written to HBM, invalidated at the kernel boundary and re-read cold before
+// the V stream starts.  Here the scores stay in LDS and there is one launch.
+//   A: a quad per key position (64 positions per step, KS steps per round), lane qd owning 16 dims: the
+//      k_attn_scores sums (ascending f, x..w, then the two DPP quad steps), the same scale and mask
+//      rounding; two rounds of K rows are in flight (round g + 2 is requested once round g is summed), and
+//      a round's mask values are requested with its K rows so that no load waits behind a later round;
+//   V: the first (pass, 512 positions) item of V is requested before the softmax;
+//   B: the exact max, then k_attn_pv_mp's thread-strided exponentials and f64 denominator at NTH = 256,
+//      the same wave / s_wd reduction;
+//   C: k_attn_pv_mp's items: lane t of a 16-lane row holds positions 4t + 64u in ascending u, f64
+//      accumulation, the DPP row reduction.
+// Every sum is the pair's, in its order: bit-identical to it.  (k_attn_fused runs the row kernel's
+// 1024-thread order, which differs from the pair's by up to 1 ulp.)  Every first load is unconditional with
+// a clamped address.
+constexpr int ONE_THREADS = 256;
+template <int KS, bool MASK>
+__global__ __launch_bounds__(ONE_THREADS) void k_attn_one(AttnArgs a) {
+    constexpr int NW = ONE_THREADS / 64, NTH = ONE_THREADS;
+    constexpr int F = 4;            // float4 per lane per key position (hd 64: 16 dims per quad lane)
+    constexpr int GP = 64 * KS;     // positions per K round
+    constexpr int UV = 8, NPASS = 4, KSTEP = 64 * UV;
+    extern __shared__ __attribute__((aligned(16))) float s_p[];  // (P rounded to 64) + 64 floats (launcher)
+    __shared__ float s_wf[NW];
+    __shared__ double s_wd[NW];
+    const int h = blockIdx.y, z = blockIdx.z;
+    const int b = z / a.n, tq = z - b * a.n;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane >> 4, t = lane & 15, qd = lane & 3;
+    const int P = seq_p(a, b);
+    const int hk = h / (a.H / (int)a.k.ne[2]);
+    const int bk = b / (a.B / (int)a.k.ne[3]);
+    const int hv = h / (a.H / (int)a.v.ne[2]);
+    const int bv = b / (a.B / (int)a.v.ne[3]);
+    const char * qbase = a.q.data + tq * a.q.nb[1] + (int64_t)h * a.q.nb[2] + (int64_t)b * a.q.nb[3];
+    const char * kbase = a.k.data + (int64_t)hk * a.k.nb[2] + (int64_t)bk * a.k.nb[3] + seq_koff(a, b);
+    const char * vbase = a.v.data + (int64_t)hv * a.v.nb[2] + (int64_t)bv * a.v.nb[3] + seq_voff(a, b);
+    const int64_t knb1 = a.k.nb[1], vnb1 = a.v.nb[1];
+    const float * mrow = MASK ? seq_mrow(a, b, tq, P) : nullptr;
+    const int pos0 = wave * 16 + (lane >> 2);  // this quad's position within a 64-step
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+
+    float4 kv[2][KS][F];
+    float mk[2][KS];
+    auto load_k = [&](auto BS, int i0) __attribute__((always_inline)) {
+        constexpr int bs = decltype(BS)::value;
+#pragma unroll
+        for (int u = 0; u < KS; ++u) {
+            const int i = min(i0 + 64 * u + pos0, P - 1);
+#pragma unroll
+            for (int c = 0; c < F; ++c) kv[bs][u][c] = TTS_KVLOAD((const float4 *)(kbase + (int64_t)i * knb1 + 16 * (F * qd + c)));
+            if (MASK) mk[bs][u] = *gptr(mrow + i);
+        }
+    };
+    // q first: the first sum needs it, and a wait for it must not cover the K rounds behind it
+    float qv[F][4];
+#pragma unroll
+    for (int c = 0; c < F; ++c)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) qv[c][e] = ((const float *)qbase)[16 * qd + 4 * c + e];
+    TTS_PIN_LOADS();
+    load_k(I0{}, 0);
+    load_k(I1{}, GP);
+    TTS_PIN_LOADS();
+
+    // ---- A: w[i] = f32(f32(sum_d f32(K[d,i] * q[d]) in f64) * scale) (+ mask) -> LDS, and the max ----
+    float mx = -INFINITY;
+    auto score = [&](auto BS, int i0) __attribute__((always_inline)) {
+        constexpr int bs = decltype(BS)::value;
+#pragma unroll
+        for (int u = 0; u < KS; ++u) {
+            double s = 0.0;
+#pragma unroll
+            for (int c = 0; c < F; ++c) {
+                s += (double)__fmul_rn(kv[bs][u][c].x, qv[c][0]);
+                s += (double)__fmul_rn(kv[bs][u][c].y, qv[c][1]);
+                s += (double)__fmul_rn(kv[bs][u][c].z, qv[c][2]);
+                s += (double)__fmul_rn(kv[bs][u][c].w, qv[c][3]);
+            }
+            s += dpp_f64<DPP_XOR1>(s);
+            s += dpp_f64<DPP_XOR2>(s);
+            const int i = i0 + 64 * u + pos0;
+            if (i < P) {
+                float w = __fmul_rn((float)s, a.scale);
+                if (MASK) w = __fadd_rn(w, __fmul_rn(1.0f, mk[bs][u]));
+                if (qd == 0) s_p[i] = w;
+                mx = fmaxf(mx, w);
+            }
+        }
+    };
+    // Both rounds of the loop body are loaded unconditionally (clamped), so every path into a sum has the same
+    // loads in flight and the waits stay exact: a round past the end (an odd round count) re-reads row P - 1.
+    int i0 = 0;
+    for (; i0 + 2 * GP < P; i0 += 2 * GP) {
+        score(I0{}, i0);
+        load_k(I0{}, i0 + 2 * GP);
+        TTS_PIN_LOADS();
+        score(I1{}, i0 + GP);
+        load_k(I1{}, i0 + 3 * GP);
+        TTS_PIN_LOADS();
+    }
+    score(I0{}, i0);  // the last two rounds: nothing more to request
+    score(I1{}, i0 + GP);
+
+    // ---- V: the first item is requested before the softmax (k_attn_pv_mp's items and buffers) ----
+    const int ilast = ((P - 1) >> 2) << 2;
+    const int d0 = wave * 4 + r;
+    const int nck = (P + KSTEP - 1) / KSTEP;  // items per pass
+    const int nit = NPASS * nck;
+    float4 w4[2][UV];
+    auto load_v = [&](auto BUF, int j) __attribute__((always_inline)) {
+        constexpr int bf = decltype(BUF)::value;
+        const int pass = j / nck, k0 = (j - pass * nck) * KSTEP;
+        const char * vrow = vbase + (int64_t)min(d0 + pass * 4 * NW, a.hd - 1) * vnb1;
+#pragma unroll
+        for (int u = 0; u < UV; ++u) w4[bf][u] = TTS_KVLOAD((const float4 *)(vrow + 4 * (int64_t)min(k0 + 64 * u + 4 * t, ilast)));
+    };
+    load_v(I0{}, 0);
+    TTS_PIN_LOADS();
+
+    // ---- B: the max (exact in any order), then k_attn_pv_mp's softmax at NTH = 256 ----
+    mx = fmaxf(mx, dpp_f32<DPP_XOR1>(mx));
+    mx = fmaxf(mx, dpp_f32<DPP_XOR2>(mx));
+    mx = fmaxf(mx, dpp_f32<DPP_HALF_MIRROR>(mx));
+    mx = fmaxf(mx, dpp_f32<DPP_MIRROR>(mx));
+    mx = fmaxf(fmaxf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(mx), 0)), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mx), 16))),
+               fmaxf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(mx), 32)), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mx), 48))));
+    if (lane == 0) s_wf[wave] = mx;
+    __syncthreads();  // the scores and the wave maxima
+    mx = s_wf[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) mx = fmaxf(mx, s_wf[w]);
+    double sum = 0.0;
+    for (int i = tid; i < P; i += NTH) {
+        const float e = cr_expf(__fsub_rn(s_p[i], mx));
+        s_p[i] = e;
+        sum += (double)e;
+    }
+    sum = wave_sum_f64(sum);
+    if (lane == 0) s_wd[wave] = sum;
+    __syncthreads();
+    sum = 0.0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) sum += s_wd[w];
+    const float inv = (float)(1.0 / sum);
+    const int P64 = (P + 63) & ~63;
+    for (int i = tid; i < P64; i += NTH) s_p[i] = i < P ? __fmul_rn(s_p[i], inv) : 0.f;
+    __syncthreads();
+
+    // ---- C: out[d] = sum_i (f32)(p[i] * V[d,i]) in f64, item by item ----
+    double acc = 0.0;
+    auto item_sum = [&](auto BUF, int j) __attribute__((always_inline)) {
+        constexpr int bf = decltype(BUF)::value;
+        const int pass = j / nck, k0 = (j - pass * nck) * KSTEP;
+#pragma unroll
+        for (int u = 0; u < UV; ++u) {
+            const int i = k0 + 64 * u + 4 * t;
+            const float4 pp = *(const float4 *)(s_p + min(i, P64 - 4));
+            const float4 vq = w4[bf][u];
+            acc += i + 0 < P ? (double)__fmul_rn(pp.x, vq.x) : 0.0;
+            acc += i + 1 < P ? (double)__fmul_rn(pp.y, vq.y) : 0.0;
+            acc += i + 2 < P ? (double)__fmul_rn(pp.z, vq.z) : 0.0;
+            acc += i + 3 < P ? (double)__fmul_rn(pp.w, vq.w) : 0.0;
+        }
+        if (k0 + KSTEP < P) return;  // the pass continues in the next item (uniform)
+        acc += dpp_f64<DPP_XOR1>(acc);
+        acc += dpp_f64<DPP_XOR2>(acc);
+        acc += dpp_f64<DPP_HALF_MIRROR>(acc);
+        acc += dpp_f64<DPP_MIRROR>(acc);
+        const int d = d0 + pass * 4 * NW;
+        if (t == 0 && d < a.hd) {
+            const int64_t o = ((int64_t)tq * a.H + h) * a.hd + d;
+            a.out[(int64_t)b * a.obs + o] = (float)acc;
+            if (a.out2) a.out2[(int64_t)b * a.n * a.H * a.hd + o] = (float)acc;
+        }
+        acc = 0.0;
+    };
+    for (int j = 0; j < nit; j += 2) {
+        if (j + 1 < nit) load_v(I1{}, j + 1);
+        item_sum(I0{}, j);
+        if (j + 1 >= nit) break;
+        if (j + 2 < nit) load_v(I0{}, j + 2);
+        item_sum(I1{}, j + 1);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // Fused decode attention for long contexts: ONE launch per attention, one 1024-thread workgroup per
 // (head, query, sequence).  The split pair above pays two launch ramps and an L2 round trip of the
 // scores; here every byte of K and V is requested as early as registers allow:
@@ -1105,6 +1295,26 @@ void launch_attn_decode(tts_hip_backend * be, const TD & q, const TD & k, const 
         const int nch = (P + 128 * KS - 1) / (128 * KS);
         const int pstride = (P + 63) & ~63;
         const size_t rows = (size_t)H * n * B;
+        // the one-launch kernel, only where the four-wave all-dims P.V (k_attn_pv_mp<8, 4, 4>) would run: its sums
+        if (be->attn_one && vvec_all && hd == 64 && be->attn_pv_mp == 1 && (P <= 512 || rows >= (size_t)be->cus) &&
+            rows * ((size_t)pstride + nch) <= be->attn_floats) {
+            const dim3 g3(1u, (unsigned)H, (unsigned)(n * B));
+            const uint32_t pl = (uint32_t)((pstride + 64) * sizeof(float));  // s_p
+            hipEvent_t e0 = nullptr, e1 = nullptr;
+            if (be->profile_gemv) profile_pair(be, e0, e1);
+            // TTS_HIP_OPT_ATTN_ONE: 1 = two rounds of 128 key positions in flight, 2 = of 256
+            if (be->attn_one == 2) {
+                if (mask) hipExtLaunchKernelGGL((k_attn_one<4, true>), g3, dim3(ONE_THREADS), pl, be->stream, e0, e1, 0u, a);
+                else hipExtLaunchKernelGGL((k_attn_one<4, false>), g3, dim3(ONE_THREADS), pl, be->stream, e0, e1, 0u, a);
+            } else {
+                if (mask) hipExtLaunchKernelGGL((k_attn_one<2, true>), g3, dim3(ONE_THREADS), pl, be->stream, e0, e1, 0u, a);
+                else hipExtLaunchKernelGGL((k_attn_one<2, false>), g3, dim3(ONE_THREADS), pl, be->stream, e0, e1, 0u, a);
+            }
+            TTS_HIP_CHECK(hipGetLastError());
+            if (be->profile_gemv)
+                profile_push(be, e0, e1, (double)rows * (2.0 * P * hd + 2.0 * hd) * 4.0, TTS_PROF_ATTN);
+            return;
+        }
         if (rows * ((size_t)pstride + nch) <= be->attn_floats) {
             float * sbuf = be->attn_buf;
             float * mxbuf = be->attn_buf + rows * pstride;
@@ -1172,3 +1382,27 @@ void launch_attn_decode(tts_hip_backend * be, const TD & q, const TD & k, const 
 }
 
 }  // namespace tts
+
+extern "C" int tts_hip_attn_decode(tts_hip_backend_t be, const tts_tensor * q, const tts_tensor * k, const tts_tensor * v,
+                                   const float * mask, int64_t mbs, float scale, float * out, float * out2, const int64_t * koff,
+                                   const int64_t * voff, const int64_t * moff, const int32_t * pseq) {
+    if (!be || !q || !k || !v || !out || !q->data || !k->data || !v->data) return TTS_STATUS_BAD_ARG;
+    if (q->type != TTS_TYPE_F32 || k->type != TTS_TYPE_F32 || v->type != TTS_TYPE_F32) return TTS_STATUS_BAD_ARG;
+    const int64_t hd = q->ne[0], n = q->ne[1], H = q->ne[2], B = q->ne[3], P = k->ne[1];
+    if (hd <= 0 || hd % 4 || n <= 0 || H <= 0 || B <= 0 || P <= 0 || P > tts::ATTN_MAXP) return TTS_STATUS_BAD_ARG;
+    if (k->ne[0] != hd || v->ne[0] != P || v->ne[1] != hd) return TTS_STATUS_BAD_ARG;
+    // heads and sequences of K / V divide the query's (GQA, shared cross-attention caches)
+    if (k->ne[2] <= 0 || H % k->ne[2] || v->ne[2] <= 0 || H % v->ne[2]) return TTS_STATUS_BAD_ARG;
+    if (k->ne[3] <= 0 || B % k->ne[3] || v->ne[3] <= 0 || B % v->ne[3]) return TTS_STATUS_BAD_ARG;
+    const bool ragged = koff || voff || moff || pseq;
+    if (ragged && (!koff || !voff || !pseq || (mask && !moff))) return TTS_STATUS_BAD_ARG;
+    hipSetDevice(be->device);
+    tts::TD tq = tts::make_td(q), tk = tts::make_td(k), tv = tts::make_td(v);
+    if (ragged) {  // each sequence's own view: koff / voff
+        tk.ne[3] = B, tk.nb[3] = 0;
+        tv.ne[3] = B, tv.nb[3] = 0;
+    }
+    tts::launch_attn_decode(be, tq, tk, tv, mask, scale, out, (int)hd, (int)P, (int)H, (int)n, (int)B, out2, -1, mbs, koff, voff,
+                            mask ? moff : nullptr, pseq);
+    return TTS_STATUS_SUCCESS;
+}

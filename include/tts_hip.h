@@ -349,6 +349,14 @@ enum tts_hip_option {
                                      a 256-thread workgroup per (head, query, sequence) that keeps the scores in LDS (k_attn_one: the
                                      split pair's sums in its order, bit-identical), two rounds of 128 key positions in flight;
                                      2 = rounds of 256 positions; 0 = the split pair (k_attn_scores + k_attn_pv_mp) */
+    TTS_HIP_OPT_GEMV_KR_TAIL = 44, /* the tail of the K-relay Q4_K kernel (one tile per workgroup, no SwiGLU): 1 (default) = the
+                                     residual of a fused ADD is requested at kernel entry behind the weights, and K = 1024 (one
+                                     block per wave) folds ggml's chain after ONE barrier -- every wave leaves its block's 36
+                                     terms per lane in LDS (over the operand tile, dead by then) and wave v runs the whole chain
+                                     of row v of every lane, the relay's additions in the relay's order (bit-identical);
+                                     2 = the same with the terms beside the operand tile (36 KB more LDS, one barrier fewer);
+                                     3 = the early residual alone; 4 = the fold alone; 0 = the relay and the residual read
+                                     at the store */
     TTS_HIP_OPT_COALESCE = 37,    /* 1 (default): while the process-wide coalescer is on (tts_hip_coalesce_enable), this
                                      backend's graph_compute of a one-prompt decode step may join the same step of other
                                      backends on the device as one coalesced launch (tts_hip_coalesce_stats); 0 = never */
@@ -455,6 +463,10 @@ int tts_hip_gemv(tts_hip_backend_t backend, int type, const void * w, const floa
 /* As tts_hip_gemv for a weight stored with tts_tensor flags `wflags` (TTS_FLAG_TILED: the tile layout). */
 int tts_hip_gemv_ex(tts_hip_backend_t backend, int type, const void * w, const float * x, float * y,
                     int64_t K, int64_t N, int64_t M, int32_t wflags);
+/* As tts_hip_gemv_ex with the epilogue of a MUL_MAT whose sole consumer is a residual ADD:
+ * y[M][N] = product + res[M][N] (one f32 add per element); res may be y itself.  NULL = tts_hip_gemv_ex. */
+int tts_hip_gemv_res(tts_hip_backend_t backend, int type, const void * w, const float * x, float * y, const float * res,
+                     int64_t K, int64_t N, int64_t M, int32_t wflags);
 
 /* ---- generic backend vtable: lets the same C++ runners target the HIP backend or the CPU oracle
  * (the latter lives in oracle/ and is only linked by tests and bench.py's cpu_baseline leg). ---- */

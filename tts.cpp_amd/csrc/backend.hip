@@ -806,6 +806,10 @@ extern "C" int tts_hip_set_option(tts_hip_backend_t be, int option, int value) {
             if (value < 0 || value > 2) return TTS_STATUS_BAD_ARG;
             be->attn_one = value;
             return 0;
+        case TTS_HIP_OPT_GEMV_KR_TAIL:
+            if (value < 0 || value > 4) return TTS_STATUS_BAD_ARG;
+            be->gemv_kr_tail = value;
+            return 0;
         case TTS_HIP_OPT_GEMM_KR_NW: be->gemm_kr_nw = value == 8 ? 8 : 4; return 0;
         case TTS_HIP_OPT_GEMM_Q8: be->gemm_q8 = value != 0; return 0;
         case TTS_HIP_OPT_CU_PARTITION: {

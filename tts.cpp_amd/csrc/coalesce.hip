@@ -222,6 +222,7 @@ void copy_options(tts_hip_backend * d, const tts_hip_backend * s) {
     d->gemv_mf_prequant = s->gemv_mf_prequant;
     d->gemv_kr = s->gemv_kr;
     d->gemv_kr_loop = s->gemv_kr_loop;
+    d->gemv_kr_tail = s->gemv_kr_tail;
     d->gemv_q80_pro = s->gemv_q80_pro;
     d->gemv_q80_slab = s->gemv_q80_slab;
     d->gemv_q80_rw = s->gemv_q80_rw;

@@ -3183,6 +3183,11 @@ extern "C" int tts_hip_gemv(tts_hip_backend_t be, int type, const void * w, cons
 
 extern "C" int tts_hip_gemv_ex(tts_hip_backend_t be, int type, const void * w, const float * x, float * y, int64_t K, int64_t N,
                                int64_t M, int32_t wflags) {
+    return tts_hip_gemv_res(be, type, w, x, y, nullptr, K, N, M, wflags);
+}
+
+extern "C" int tts_hip_gemv_res(tts_hip_backend_t be, int type, const void * w, const float * x, float * y, const float * res,
+                                int64_t K, int64_t N, int64_t M, int32_t wflags) {
     if (!be) return TTS_STATUS_BAD_ARG;
     if ((wflags & TTS_FLAG_TILED) && (type != TTS_TYPE_Q4_K || N % 4)) return TTS_STATUS_BAD_ARG;
     if (type == TTS_TYPE_Q4_K && K % 256) return TTS_STATUS_BAD_ARG;
@@ -3202,6 +3207,11 @@ extern "C" int tts_hip_gemv_ex(tts_hip_backend_t be, int type, const void * w, c
     j.yrs[0] = 1;
     j.x = x;
     j.xcs = K;
+    if (res) {  // the fused residual ADD of a graph's MUL_MAT -> ADD
+        j.epi = EPI_ADD;
+        j.res = res;
+        j.rcs = N;
+    }
     const bool q80pro = type == TTS_TYPE_Q8_0 && K % QK_K == 0 && M <= 8 && be->gemv_q80_pro;
     if (type == TTS_TYPE_Q4_K || q80pro) {
         j.pro = PRO_QUANT;

@@ -244,7 +244,12 @@ struct GemvJob {
     const int64_t * yoff = nullptr;
     int32_t yoff_mats = 0, yoff_ld = 0;
     int32_t xcd_cols = 0;  // many-column K-relay GEMM: a row tile's column tiles on one XCD (TTS_HIP_OPT_GEMM_KR_XCD)
+    int32_t kr_tail = 0;   // K-relay kernel: KR_TAIL_* bits (TTS_HIP_OPT_GEMV_KR_TAIL, set by its launcher)
 };
+// KR_TAIL_RES: an EPI_ADD residual is requested at kernel entry; KR_TAIL_FOLD: K = 1024 folds the chain after one
+// barrier; KR_TAIL_BESIDE: the fold's terms lie beside the operand tile in LDS instead of over it
+enum { KR_TAIL_RES = 1, KR_TAIL_FOLD = 2, KR_TAIL_BESIDE = 4 };
+constexpr int KR_FOLD_BYTES = 4 * 4 * (2 * 64 * 16 + 64 * 4);  // 4 blocks x 4 rows x (two float4 + one float per lane)
 __host__ __device__ inline int64_t job_roff(const GemvJob & j, int m) { return j.hetero ? j.roff[m] : (int64_t)m * j.N; }
 __host__ __device__ inline int64_t job_rows(const GemvJob & j) { return job_roff(j, j.nmat); }
 // In-kernel phase timestamps (s_memrealtime, 100 MHz) per wave, compiled in only by the
@@ -401,6 +406,7 @@ struct tts_hip_backend {
     int gemv_mf_prequant = 1;  // TTS_HIP_OPT_GEMV_PREQUANT
     int gemv_kr = 1;           // TTS_HIP_OPT_GEMV_KRELAY
     int gemv_kr_loop = 1;      // TTS_HIP_OPT_GEMV_KRELAY_LOOP
+    int gemv_kr_tail = 1;      // TTS_HIP_OPT_GEMV_KR_TAIL (0 .. 4; GemvJob::kr_tail carries its KR_TAIL_* bits)
     int gemv_q80_pro = 1;      // TTS_HIP_OPT_GEMV_Q80_PRO
     int gemv_q80_slab = 1;     // TTS_HIP_OPT_GEMV_Q80_SLAB
     int gemv_q80_rw = 0;       // TTS_HIP_OPT_GEMV_Q80_RW

@@ -170,6 +170,8 @@ __device__ __forceinline__ int xcd_contiguous(int b, int n) {
 // behind its prologue's activation loads).  Callers pass indices that are uniform by construction
 // through readfirstlane, and single-matrix jobs index 0.
 
+// gemv_store's write of a finished value (after the epilogue)
+__device__ __forceinline__ void gemv_put(const GemvJob & j, int mat, int64_t row, int m, float v);
 template <int MC>
 __device__ __forceinline__ void gemv_store(const GemvJob & j, int mat, int64_t row, int m, float v) {
     if (j.epi == EPI_GELU) {
@@ -180,6 +182,15 @@ __device__ __forceinline__ void gemv_store(const GemvJob & j, int mat, int64_t r
     } else if (j.epi == EPI_SILU_MUL) {
         v = __fmul_rn(dev_silu(j.res[m * j.rcs + row]), v);
     }
+    gemv_put(j, mat, row, m, v);
+}
+// gemv_store for a caller that requested the EPI_ADD residual res[m * rcs + row] itself, ahead of the product
+// (`pre`: rv holds it; otherwise gemv_store)
+__device__ __forceinline__ void gemv_store_res(const GemvJob & j, int mat, int64_t row, int m, float v, float rv, bool pre) {
+    if (pre) gemv_put(j, mat, row, m, __fadd_rn(v, rv));
+    else gemv_store<8>(j, mat, row, m, v);
+}
+__device__ __forceinline__ void gemv_put(const GemvJob & j, int mat, int64_t row, int m, float v) {
     float * const Y = j.Y[mat] + ((j.yoff_mats >> mat) & 1 ? j.yoff[mat * j.yoff_ld + m] : 0);
     const int64_t ycs = j.ycs[mat], yrs = j.yrs[mat];
     if (mat == j.rep_mat) {
@@ -1248,6 +1259,39 @@ __global__ __launch_bounds__(64 * NWT * ((SW || CP) ? 2 : 1)) void k_gemv_q4K_kr
     using B0 = std::integral_constant<int, 0>;
     using B1 = std::integral_constant<int, LOOP ? 1 : 0>;
     int64_t t = tx;
+    // TTS_HIP_OPT_GEMV_KR_TAIL (j.kr_tail; one tile per workgroup, no SwiGLU).  KR_TAIL_RES: the residual of an
+    // EPI_ADD product -- the four elements this lane would store -- is requested right behind the weights instead of
+    // at the store, after the chain.  The loads are unconditional and clamped like the weights', and a job without
+    // them re-reads the head of its weight matrix instead: every path then has the same loads in flight at every join,
+    // and the wait before the first MFMA stays a wait for the weights alone (the residual, issued last, is not in it).
+    // A lane reads exactly the elements it may later write, so an output that is the residual's own buffer behaves
+    // as with the read at the store.
+    constexpr bool TAIL = !SW && !LOOP && CTW == 1 && !CP;
+    const bool res_pre = TAIL && j.epi == EPI_ADD && (j.kr_tail & KR_TAIL_RES);
+    // (the tile's matrix and rows are worked out once, before any load is in flight: a loop over the matrices
+    // behind the weight loads would wait for them, and at the store it would sit on the tail)
+    int tmat = 0;
+    int64_t trow0 = 0, trows = 0;
+    const float * rp[4] = {};
+    if constexpr (TAIL) {
+        tmat = tile_mat(t);
+        trow0 = tile_row0(t, tmat);
+        trows = job_roff(j, tmat + 1) - job_roff(j, tmat);
+        const float * const base = res_pre ? j.res + (int64_t)(c0 + cc) * j.rcs : (const float *)j.W[tmat];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t rr = trow0 + 4 * kg + q < trows ? trow0 + 4 * kg + q : trows - 1;
+            rp[q] = base + (res_pre ? rr : 0);
+        }
+    }
+    float rv[4] = {0.f, 0.f, 0.f, 0.f};
+    auto load_res = [&]() __attribute__((always_inline)) {
+        if constexpr (TAIL) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) rv[q] = *gptr(rp[q]);
+            TTS_PIN_LOADS();
+        }
+    };
     if constexpr (PRO == PRO_COPY) {
         // operands by LDS-DMA, then this wave's weights (unconditional, clamped)
         const int nck = (int)((ntile * bqb) >> 10);
@@ -1256,8 +1300,12 @@ __global__ __launch_bounds__(64 * NWT * ((SW || CP) ? 2 : 1)) void k_gemv_q4K_kr
                                              (__attribute__((address_space(3))) void *)(smem + (size_t)i * 1024), 16, 0, 0);
         TTS_PIN_LOADS();
         load_w(B0{}, t);
+        load_res();
     } else {
-        auto first = [&]() __attribute__((always_inline)) { load_w(B0{}, t); };
+        auto first = [&]() __attribute__((always_inline)) {
+            load_w(B0{}, t);
+            load_res();
+        };
         ProOv ov;  // a column tile (j.bq_tile: the many-column GEMM at decode sizes) quantizes its own columns
         ov.col0 = c0;
         ov.mcols = M;
@@ -1394,15 +1442,63 @@ __global__ __launch_bounds__(64 * NWT * ((SW || CP) ? 2 : 1)) void k_gemv_q4K_kr
                 }
             }
         } else if (w == nwt - 1) {
-            const int mat = tile_mat(tt);
-            const int64_t row0 = tile_row0(tt, mat);
-            const int64_t rows_m = job_roff(j, mat + 1) - job_roff(j, mat);
+            const int mat = TAIL ? tmat : tile_mat(tt);
+            const int64_t row0 = TAIL ? trow0 : tile_row0(tt, mat);
+            const int64_t rows_m = TAIL ? trows : job_roff(j, mat + 1) - job_roff(j, mat);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int64_t rr = row0 + 4 * kg + q;
-                if (r < M && rr < rows_m) gemv_store<8>(j, mat, rr, c0 + r, tot[q]);
+                if (r < M && rr < rows_m) gemv_store_res(j, mat, rr, c0 + r, tot[q], rv[q], res_pre);
             }
         }
+    };
+
+    // KR_TAIL_FOLD (K = 1024: one block per wave, four waves): the relay hands 36 running sums per lane through LDS
+    // three times in series -- three barriers and three LDS round trips to fold four blocks.  Here every wave leaves
+    // its block's 36 terms per lane in LDS, and after ONE barrier wave v runs the whole chain of row 4 kg + v of
+    // every lane: sums[l] = 0 + p_l(block 0) + p_l(1) + p_l(2) + p_l(3), sumf = 0 - q(0) - q(1) - q(2) - q(3), then
+    // sumf + sums[0..7] -- every addition of the relay, the initial 0 + included (a -0 term comes out as +0, as
+    // there), in the relay's order: bit-identical.  Each wave stores its own row.
+    // The terms lie over the operand tile, which is dead once every wave has read its operands (one more barrier,
+    // right after the MFMAs' operand reads, and no more LDS than the tile), or with KR_TAIL_BESIDE next to it.
+    // Block b, row q: [64 lanes] float4 p_0..3, [64 lanes] float4 p_4..7, [64 lanes] q.
+    auto fold_store = [&](int64_t tt) __attribute__((always_inline)) {
+        const bool beside = j.kr_tail & KR_TAIL_BESIDE;
+        float * const fb = beside ? relay : (float *)smem;
+        constexpr int FQ = 2 * 64 * 4 + 64;  // floats per (block, row)
+        if (!beside) __syncthreads();        // every wave has read its operands
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float * const p = fb + (size_t)(w * 4 + q) * FQ;
+            const int hq = q >> 1, e = q & 1;
+            *(float4 *)(p + lane * 4) = make_float4(tp[0][0][hq][e], tp[0][1][hq][e], tp[0][2][hq][e], tp[0][3][hq][e]);
+            *(float4 *)(p + 256 + lane * 4) = make_float4(tp[0][4][hq][e], tp[0][5][hq][e], tp[0][6][hq][e], tp[0][7][hq][e]);
+            p[512 + lane] = tq[0][hq][e];
+        }
+        __syncthreads();
+        float4 pa[4], pb[4];
+        float pq[4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const float * const p = fb + (size_t)(b * 4 + w) * FQ;
+            pa[b] = *(const float4 *)(p + lane * 4);
+            pb[b] = *(const float4 *)(p + 256 + lane * 4);
+            pq[b] = p[512 + lane];
+        }
+        float sums[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, sumf = 0.f;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const float pl[8] = {pa[b].x, pa[b].y, pa[b].z, pa[b].w, pb[b].x, pb[b].y, pb[b].z, pb[b].w};
+#pragma unroll
+            for (int l = 0; l < 8; ++l) sums[l] = __fadd_rn(sums[l], pl[l]);
+            sumf = __fsub_rn(sumf, pq[b]);
+        }
+        float tot = sumf;
+#pragma unroll
+        for (int l = 0; l < 8; ++l) tot = __fadd_rn(tot, sums[l]);
+        const int64_t rr = trow0 + 4 * kg + w;
+        const float rw = w == 0 ? rv[0] : w == 1 ? rv[1] : w == 2 ? rv[2] : rv[3];
+        if (r < M && rr < trows) gemv_store_res(j, tmat, rr, c0 + r, tot, rw, res_pre);
     };
 
     if constexpr (LOOP) {
@@ -1423,7 +1519,12 @@ __global__ __launch_bounds__(64 * NWT * ((SW || CP) ? 2 : 1)) void k_gemv_q4K_kr
     } else {
         terms(B0{});
         TTS_TS(j, 3);
-        relay_store(t);
+        if constexpr (TAIL && BPW == 1 && NWT == 4) {
+            if ((j.kr_tail & KR_TAIL_FOLD) && nb == 4) fold_store(t);
+            else relay_store(t);
+        } else {
+            relay_store(t);
+        }
         TTS_TS(j, 4);
         if constexpr (CTW > 1) {
             for (int k = 1; k < ntile; ++k) {  // the next column tile: same weight registers, its operands
@@ -2582,7 +2683,11 @@ static void launch_q4k_mf(tts_hip_backend * be, const GemvJob & job) {
 // ---- K-relay matrix-core path (k_gemv_q4K_kr) ----
 static size_t q4k_kr_lds(int64_t bq_bytes, bool sw) { return (size_t)((bq_bytes + 15) & ~15) + (sw ? 2 * 64 * 36 * 4 + 64 * 16 : 64 * 36 * 4); }
 template <int BPW, bool SW, int NWT, bool LANE = false, bool LOOP = false, int PRO = PRO_COPY, int CTW = 1, bool CP = false>
-static void launch_q4k_kr_t(tts_hip_backend * be, const GemvJob & j, unsigned gx, unsigned gy = 1) {
+static void launch_q4k_kr_t(tts_hip_backend * be, const GemvJob & job, unsigned gx, unsigned gy = 1) {
+    // TTS_HIP_OPT_GEMV_KR_TAIL -> the kernel's KR_TAIL_* bits (the one-tile, no-SwiGLU variants read them)
+    static const int tail_bits[5] = {0, KR_TAIL_RES | KR_TAIL_FOLD, KR_TAIL_RES | KR_TAIL_FOLD | KR_TAIL_BESIDE, KR_TAIL_RES, KR_TAIL_FOLD};
+    GemvJob j = job;
+    j.kr_tail = tail_bits[be->gemv_kr_tail];
     if constexpr (PRO == PRO_COPY && CTW == 1 && !CP) {  // in-kernel prologue (launch_q4k_kr / launch_gemm_q4k_kr decide)
         if (j.pro == PRO_LN) return launch_q4k_kr_t<BPW, SW, NWT, LANE, LOOP, PRO_LN>(be, j, gx, gy);
         if (j.pro == PRO_QUANT) return launch_q4k_kr_t<BPW, SW, NWT, LANE, LOOP, PRO_QUANT>(be, j, gx, gy);
@@ -2597,7 +2702,14 @@ static void launch_q4k_kr_t(tts_hip_backend * be, const GemvJob & j, unsigned gx
     }
     static std::atomic<uint32_t> attr_done{0};
     set_lds_attr_once(attr_done, be->device, (const void *)k_gemv_q4K_kr<BPW, SW, NWT, LANE, LOOP, PRO, CTW, CP>);
-    const size_t lds = q4k_kr_lds((CP ? 2 : CTW) * (j.bq_tile ? j.bq_tile : j.bq_bytes), SW || CP);
+    size_t lds = q4k_kr_lds((CP ? 2 : CTW) * (j.bq_tile ? j.bq_tile : j.bq_bytes), SW || CP);
+    if constexpr (!SW && !LOOP && CTW == 1 && !CP && BPW == 1 && NWT == 4) {
+        // the one-barrier fold keeps 4 blocks x 36 terms per lane: over the operand tile, or beside it
+        if ((j.kr_tail & KR_TAIL_FOLD) && j.K == 4 * QK_K) {
+            const size_t ops = lds - 64 * 36 * 4;
+            lds = (j.kr_tail & KR_TAIL_BESIDE) ? ops + KR_FOLD_BYTES : std::max(ops, (size_t)KR_FOLD_BYTES);
+        }
+    }
     const dim3 blk(64 * NWT * ((SW || CP) ? 2 : 1));
     if (be->profile_gemv) {
         hipEvent_t e0, e1;

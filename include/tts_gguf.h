@@ -131,6 +131,15 @@ tts_parler * tts_parler_create_from_gguf(const tts_backend_iface * be, const tts
  * for dac_cfg when not NULL -- the F32 input of the quantize tool in the tests. */
 int tts_parler_write_synthetic_gguf(const tts_parler_config * cfg, const tts_dac_config * dac_cfg, const char * path);
 
+/* t5_encoder::prep_constants (t5encoder.* keys; t5encoder.vocab_size is required) + what the tensors carry:
+ * ffn_size from enc.blk.0.ffn_up, head_size from attn_q, has_down_proj from t5encoder.down_proj's presence,
+ * weight_type from attn_q (F32 / F16).  seed and arena stay as given.  0 on success. */
+int tts_t5_config_from_gguf(const tts_gguf * g, tts_t5_config * cfg);
+/* A T5 encoder runner whose weights are the file's "t5encoder.*" tensors. */
+tts_t5 * tts_t5_create_from_gguf(const tts_backend_iface * be, const tts_t5_config * cfg, const tts_gguf * g);
+/* Writes the synthetic weights tts_t5_create uploads for cfg with the reference's tensor names and keys. */
+int tts_t5_write_synthetic_gguf(const tts_t5_config * cfg, const char * path);
+
 /* dac_model::prep_constants / prep_layers: codebooks, strides from the dac.* keys.  0 on success. */
 int tts_dac_config_from_gguf(const tts_gguf * g, tts_dac_config * cfg);
 /* A DAC decoder whose weights are the file's "audio_encoder.*" tensors (F32). */

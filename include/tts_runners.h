@@ -85,6 +85,55 @@ uint64_t tts_parler_weight(tts_parler * p, int32_t i, char * name, uint64_t name
 uint64_t tts_parler_get_node(tts_parler * p, const char * name, void * dst, uint64_t cap);
 /* Debug: node i of the last graph: op / type / ne; copies its bytes when contiguous (returns size). */
 uint64_t tts_parler_node(tts_parler * p, int32_t i, int32_t * op, int32_t * type, int64_t * ne, void * dst, uint64_t cap);
+/* A voice description at run time (parler_tts_runner::update_conditional_prompt): uploads encoding
+ * [n][hidden_size] (the T5 encoder's output, tts_t5_encode) into text_encoding, recomputes every layer's
+ * cross K / V (prep_cross_key_values) and resets positions as tts_parler_reset does.  The cross caches,
+ * masks and recorded graphs are sized by cfg.n_encode: n must equal it (a caller who wants an N-token
+ * description creates the runner with n_encode = N).  Returns non-zero, with nothing changed, when
+ * n != cfg.n_encode or cross-attention is off.  Every sequence of a lock-step batch shares the description. */
+int tts_parler_set_conditional_prompt(tts_parler * p, const float * encoding, int32_t n);
+
+/* T5 voice-description encoder (t5_runner, src/models/parler/t5/model.cpp; defaults = t5_encoder,
+ * t5/model.h:42-51: flan-t5-xl with the down projection to Parler's hidden size). */
+typedef struct tts_t5_config {
+    int32_t n_layers;              /* 24 */
+    int32_t hidden_size;           /* 2048 */
+    int32_t n_attn_heads;          /* 32 */
+    int32_t head_size;             /* 64 */
+    int32_t ffn_size;              /* 5120 (flan-t5-xl; the reference reads it from the tensors) */
+    int32_t relative_attn_buckets; /* 32 */
+    int32_t vocab_size;            /* 32128 (flan-t5; a required key in the file) */
+    int32_t max_context_length;    /* 512 */
+    int32_t output_size;           /* 1536 (down_proj rows; = hidden_size without down_proj) */
+    int32_t has_down_proj;         /* 1 */
+    int32_t weight_type;           /* TTS_TYPE_F32 or TTS_TYPE_F16 matrices (norms, relative bias, down_proj_bias: F32) */
+    int32_t eos_token_id;          /* 1 (the caller appends it: tts_t5_encode takes ids, not text) */
+    uint64_t seed;                 /* synthetic weight seed base (0x5EED) */
+    uint64_t arena_bytes;          /* compute arena (0 = sized for max_context_length tokens) */
+    int32_t debug_no_reuse;        /* 1 = every node keeps its own arena memory (node dumps) */
+    int32_t pad_;
+} tts_t5_config;
+
+typedef struct tts_t5 tts_t5;
+
+void tts_t5_default_config(tts_t5_config * cfg);
+tts_t5 * tts_t5_create(const tts_backend_iface * be, const tts_t5_config * cfg);
+void tts_t5_free(tts_t5 * t);
+/* t5_runner::run: tokens [n] (EOS included, 1 <= n <= max_context_length) -> out [n][output_size]. */
+int tts_t5_encode(tts_t5 * t, const int32_t * tokens, int32_t n, float * out);
+int32_t tts_t5_output_size(const tts_t5 * t);
+int32_t tts_t5_last_graph_nodes(const tts_t5 * t);
+uint64_t tts_t5_weight_bytes(const tts_t5 * t);
+/* Weight introspection for tests, as tts_parler_weight. */
+int32_t tts_t5_n_weights(const tts_t5 * t);
+uint64_t tts_t5_weight(tts_t5 * t, int32_t i, char * name, uint64_t name_cap, int64_t * ne, int32_t * type, void * dst, uint64_t cap);
+/* The last graph's node list (valid until the next encode), e.g. for tts_hip_plan_stats. */
+tts_tensor * const * tts_t5_graph(const tts_t5 * t, int32_t * n_nodes);
+/* Debug: bytes of a named tensor of the last graph ("pos_bucket": the I32 [n][n] bucket input, "pos_bias",
+ * "t5_output"); returns its size (copied when cap suffices), 0 if absent. */
+uint64_t tts_t5_get_node(tts_t5 * t, const char * name, void * dst, uint64_t cap);
+/* Debug: node i of the last graph: op / type / ne; copies its bytes when contiguous (returns size). */
+uint64_t tts_t5_node(tts_t5 * t, int32_t i, int32_t * op, int32_t * type, int64_t * ne, void * dst, uint64_t cap);
 
 /* Orpheus-3B decoder config (defaults = orpheus_model, src/models/orpheus/model.h:31-46; rope
  * factors from Llama-3.2 rope scaling as py-gguf/tts_encoders/orpheus_gguf_encoder.py:144-173). */

@@ -1,0 +1,66 @@
+"""The T5 attention chain (t5/model.cpp:246-265) as a tests/nodes.py graph, shared by the planner test
+(test_t5_cpu.py) and the kernel test (test_attn_bias_gpu.py):
+
+  cont(permute(k)) -> mul_mat(k, permute(q)) -> add(bias) -> soft_max_ext(mask, 1.0, 0)
+    -> mul_mat(kq, cont_3d(transpose(v))) -> permute(2, 0, 1, 3) -> cont
+"""
+import numpy as np
+
+import ttship
+
+F32 = ttship.F32
+
+
+def inputs(P, n, H, hd, seed=None):
+    """Random q (n, H, hd), k (P, H, hd), v (P, H * hd), bias (H, n, P) and a zero mask (n, P) with one
+    -inf key when P > 4."""
+    rng = np.random.default_rng(P * 1000 + n * 10 + H + hd if seed is None else seed)
+    q = rng.standard_normal((n, H, hd)).astype(np.float32)
+    k = rng.standard_normal((P, H, hd)).astype(np.float32)
+    v = rng.standard_normal((P, H * hd)).astype(np.float32)
+    bias = (2.0 * rng.standard_normal((H, n, P))).astype(np.float32)
+    mask = np.zeros((n, P), np.float32)
+    if P > 4:
+        mask[:, P // 3] = -np.inf
+    return q, k, v, bias, mask
+
+
+def build(g, q, k, v, bias, mask, out_on=None):
+    """Adds the chain to Graph g; returns the output node, ne [hd, H, n].  out_on = "q" / "k" / "v" (P == n):
+    the output's memory is that input's, as a graph allocator hands it on once its last reader has run."""
+    n, H, hd = q.shape
+    P = k.shape[0]
+    leaves = {"q": g.leaf(q), "k": g.leaf(k), "v": g.leaf(v)}
+    kp = g.permute(leaves["k"], (0, 2, 1, 3))                    # [hd, P, H]
+    kc = g.node("CONT", F32, [hd, P, H], [kp])
+    qp = g.permute(leaves["q"], (0, 2, 1, 3))                    # [hd, n, H], not made contiguous (as T5's)
+    kq = g.node("MUL_MAT", F32, [P, n, H], [kc, qp])
+    kqb = g.node("ADD", F32, [P, n, H], [kq, g.leaf(bias)])      # bias ne [P, n, H]
+    sm = g.node("SOFT_MAX", F32, [P, n, H], [kqb, g.leaf(mask)], fparams={0: 1.0, 1: 0.0})
+    vt = g.transpose(leaves["v"])                                # [P, H * hd]
+    vc = g.node("CONT", F32, [P, hd, H], [vt])                   # cont_3d
+    kqv = g.node("MUL_MAT", F32, [n, hd, H], [sm, vc])
+    merged = g.permute(kqv, (2, 0, 1, 3))                        # [hd, H, n]
+    if out_on is None:
+        return g.node("CONT", F32, [hd, H, n], [merged])
+    assert P == n
+    host = leaves[out_on]
+    out = g._new(F32, [hd, H, n], op=ttship.OP["CONT"], srcs=(merged,))
+    out._root, out._root_offs, out.data = host, 0, host.data     # (run_hip points it at the leaf's device copy)
+    g.arrays_alias = getattr(g, "arrays_alias", {})
+    g.arrays_alias[id(out)] = host
+    g.nodes.append(out)
+    return out
+
+
+def result(g, out):
+    """The output's values, [n, H, hd]."""
+    host = getattr(g, "arrays_alias", {}).get(id(out))
+    if host is None:
+        return g.node_array(out)
+    n = int(np.prod([out.ne[i] for i in range(4)]))
+    return g.arrays[id(host)][: 4 * n].view(np.float32).copy().reshape([out.ne[i] for i in range(3, -1, -1)])
+
+
+def plan(g, mask=None):
+    return ttship.plan_stats(g.node_ptrs(), len(g.nodes), ttship.FUSE_ALL if mask is None else mask)

@@ -162,6 +162,7 @@ void tts_hip_backend_free(tts_hip_backend_t be) {
     if (be->sample_cand) hipFree(be->sample_cand);
     if (be->repack_tmp) hipFree(be->repack_tmp);
     for (char * r : be->repack_retired) hipFree(r);
+    if (be->attn_stage) hipFree(be->attn_stage);
     for (auto & ex : be->gsig_exec)
         if (ex) hipGraphExecDestroy(ex);
     for (auto & ex : be->pexec)

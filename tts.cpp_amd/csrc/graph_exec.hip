@@ -34,6 +34,8 @@ void launch_attn_decode(tts_hip_backend * be, const TD & q, const TD & k, const 
                         float * out, int hd, int P, int H, int n, int B, float * out2, int64_t obs = -1, int64_t mbs = 0,
                         const int64_t * koff = nullptr, const int64_t * voff = nullptr, const int64_t * moff = nullptr,
                         const int * pseq = nullptr);
+void launch_attn_bias(tts_hip_backend * be, const TD & q, const TD & k, const TD & v, const float * bias, const float * mask,
+                      float scale, float * out, int P, int H, int n);
 void launch_layernorm(tts_hip_backend * be, const tts_tensor * dst, const tts_tensor * x, const float * w, const float * b,
                       float eps, bool rms);
 }  // namespace tts
@@ -160,6 +162,8 @@ struct Item {
     bool fused = false;     // ATTN: launched by the GEMV item that produces its query
     // ATTN
     const tts_tensor *q = nullptr, *k = nullptr, *v = nullptr, *mask = nullptr, *out = nullptr;
+    const tts_tensor * bias = nullptr;  // added to KQ before the softmax (k_attn_bias), [P, n, H]
+    bool stage = false;     // ATTN with a bias: out overlaps an operand; written to be->attn_stage, then copied
     float scale = 1.f;
     // LN
     const tts_tensor *x = nullptr, *w = nullptr, *b = nullptr, *dst = nullptr;
@@ -398,6 +402,7 @@ struct Planner {
             if (nx < 0 || act[nx] <= 0) continue;
             Item & A = items[a - 1];
             Item & G = items[act[nx] - 1];
+            if (A.bias) continue;  // k_attn_bias writes no private copy
             if (G.kind != Item::GEMV || G.ln || G.mms[0]->src[0]->type != TTS_TYPE_Q4_K) continue;
             const tts_tensor * x = G.mms[0]->src[1];
             if (x->data != A.out->data || !contiguous(x) || tbytes(x) != tbytes(A.out)) continue;
@@ -412,7 +417,7 @@ struct Planner {
     void fuse_xattn() {
         for (size_t ai = 0; ai < items.size(); ++ai) {
             Item & A = items[ai];
-            if (A.kind != Item::ATTN || A.k->ne[1] > 64 || A.q->ne[0] != 64 || A.q->ne[1] != 1) continue;
+            if (A.kind != Item::ATTN || A.bias || A.k->ne[1] > 64 || A.q->ne[0] != 64 || A.q->ne[1] != 1) continue;
             const tts_tensor * Q = A.q;
             const tts_tensor * t = Q;
             int hops = 0;
@@ -1846,6 +1851,20 @@ struct Planner {
         const tts_tensor * S = nodes[i];
         const tts_tensor * KQ = S->src[0];
         const tts_tensor * mask = S->src[1];
+        // soft_max(add(KQ, bias)) (T5's relative position bias, t5/model.cpp:256-259): the ADD is fused too,
+        // within k_attn_bias' range (hd 64, P <= 512, one sequence: checked below)
+        const tts_tensor * bias = nullptr;
+        int skip_add = -1;
+        if (KQ && KQ->op == TTS_OP_ADD && uses[KQ] == 1 && KQ->src[0] && KQ->src[1] && KQ->src[0]->op == TTS_OP_MUL_MAT) {
+            const tts_tensor * A = KQ;
+            const tts_tensor * bb = A->src[1];
+            if (bb->type != TTS_TYPE_F32 || A->type != TTS_TYPE_F32 || !contiguous(bb) || A->ne[3] != 1) return;
+            for (int d = 0; d < 4; ++d)
+                if (bb->ne[d] != A->src[0]->ne[d] || A->ne[d] != bb->ne[d]) return;  // a broadcast bias stays unfused
+            bias = bb;
+            skip_add = index[A];
+            KQ = A->src[0];
+        }
         if (!KQ || KQ->op != TTS_OP_MUL_MAT || uses[KQ] != 1) return;
         if (opf(S, 1) != 0.0f) return;  // ALiBi not used by TTS graphs
         const tts_tensor * KQV = sole_consumer(S);
@@ -1869,7 +1888,9 @@ struct Planner {
             while (t->view_src) t = t->view_src;
             return t->op == TTS_OP_NONE;
         };
-        if (V->op == TTS_OP_CONT && uses[V] == 1 && V->src[0] && V->src[0]->data && leaf_backed(V->src[0])) {
+        // (with a bias: the transpose of the V projection's output, an arena tensor; the span check below
+        // covers it, and with its CONT skipped nothing runs between the scores and the attention)
+        if (V->op == TTS_OP_CONT && uses[V] == 1 && V->src[0] && V->src[0]->data && (leaf_backed(V->src[0]) || bias)) {
             const tts_tensor * T = V->src[0];
             if (T->ne[3] == 1 && V->ne[0] == T->ne[0] && V->ne[1] * V->ne[2] == T->ne[1] && V->ne[3] == T->ne[2] &&
                 T->type == TTS_TYPE_F32 && V->type == TTS_TYPE_F32) {
@@ -1924,19 +1945,38 @@ struct Planner {
         // a 2-D mask serves every head and sequence; [P, rows, 1, B]: one per sequence (a ragged lock-step batch)
         if (mask && (mask->ne[1] < nq || mask->ne[2] != 1 || (mask->ne[3] != 1 && mask->ne[3] != B))) return;
         if (nq * H * B * hd != O->ne[0] * O->ne[1] * O->ne[2] * O->ne[3]) return;
+        if (bias) {  // k_attn_bias' range; anything else runs node by node
+            if (hd != 64 || P < 1 || P > 512 || B != 1 || K->ne[2] != H || K->ne[3] != 1 || V->ne[3] != 1) return;
+            if (bias->ne[0] != P || bias->ne[1] != nq || bias->ne[2] != H) return;
+            if (mask && mask->ne[3] != 1) return;
+        }
         // aliasing: O may coincide exactly with Q's storage (read-before-write per workgroup), nothing else
         const tts_tensor * Qbase = Q->view_src ? Q->view_src : Q;
-        if (overlap(O, K) || overlap(O, V) || (mask && overlap(O, mask))) return;
-        if (overlap(O, Qbase) && O->data != Qbase->data) return;
+        if (mask && overlap(O, mask)) return;
+        // With a bias every operand is an arena tensor (the projections' outputs, read in place), and the
+        // arena readily hands one's memory to the attention output, which is written while other
+        // workgroups still read them: the kernel then writes a backend buffer that is copied to the
+        // output afterwards.  (Written in place when the output's rows are the query's rows: each wave
+        // reads its query row, then writes that row.)
+        const bool q_rows = Q->data == O->data && Q->nb[0] == 4 && (int64_t)Q->nb[1] == 4 * hd * H && (int64_t)Q->nb[2] == 4 * hd;
+        const bool stage = bias && (overlap(O, K) || overlap(O, V) || overlap(O, bias) || (overlap(O, Qbase) && !q_rows));
+        if (!stage) {
+            if (overlap(O, K) || overlap(O, V)) return;
+            if (overlap(O, Qbase) && O->data != Qbase->data) return;
+        }
         // a folded operand is read where its skipped CONT would have copied it from: no node that
         // still runs between that CONT and the attention (it launches at O) may write over it
         // (the arena can hand the source's memory on once its CONT consumer has "run")
         {
             const int io = index[O];
-            const int mine[] = {i, index[KQ], index[KQV], index[PERM], skip_k, skip_q, skip_v, skip_k2, skip_v2};
+            const int mine[] = {i, index[KQ], index[KQV], index[PERM], skip_k, skip_q, skip_v, skip_k2, skip_v2, skip_add};
             // span starts at the earliest skipped CONT that read the operand (the inner one of a chain)
+            // (with a bias also the operands the skipped scores product read in place, and the bias from its
+            // ADD on: the arena may hand their memory on once those nodes have "run")
+            const int kq_at = bias ? index[KQ] : -1;
             const std::pair<const tts_tensor *, int> folded[] = {
-                {K, skip_k2 >= 0 ? skip_k2 : skip_k}, {Q, skip_q}, {V, skip_v >= 0 ? skip_v : skip_v2}};
+                {K, skip_k2 >= 0 ? skip_k2 : skip_k >= 0 ? skip_k : kq_at}, {Q, skip_q >= 0 ? skip_q : kq_at},
+                {V, skip_v >= 0 ? skip_v : skip_v2}, {bias, skip_add}};
             for (const auto & f : folded) {
                 if (f.second < 0) continue;
                 for (int j = f.second + 1; j < io; ++j) {
@@ -1953,11 +1993,14 @@ struct Planner {
         it.k = K;
         it.v = V;
         it.mask = mask;
+        it.bias = bias;
+        it.stage = stage;
         it.out = O;
         it.scale = opf(S, 0);
         act[i] = -1;
         act[index[KQ]] = -1;
         act[index[KQV]] = -1;
+        if (skip_add >= 0) act[skip_add] = -1;
         if (skip_k >= 0) act[skip_k] = -1;
         if (skip_q >= 0) act[skip_q] = -1;
         if (skip_v >= 0) act[skip_v] = -1;
@@ -2107,6 +2150,28 @@ static int run_attn_item(tts_hip_backend * be, const Item & it, const ItemTab * 
     float * out = (float *)it.out->data;
     const float * mask = it.mask ? (const float *)it.mask->data : nullptr;
     int B = (int)it.q->ne[3], P = (int)it.k->ne[1];
+    if (it.bias) {  // (never a member of a coalesced step: co_prepare refuses it)
+        if (be->bat) return TTS_STATUS_UNSUPPORTED;
+        const size_t ob = tbytes(it.out);
+        if (it.stage && be->attn_stage_size < ob) {
+            // a bigger buffer; the old one is retired, not freed: a recorded graph may still write it on
+            // replay.  Never while recording: a graph's first sighting runs eagerly and sizes the buffer.
+            if (be->stream == be->cap_stream) return TTS_STATUS_ALLOC_FAILED;
+            if (be->attn_stage) be->repack_retired.push_back((char *)be->attn_stage);
+            be->attn_stage = nullptr;
+            be->attn_stage_size = 0;
+            const size_t nbytes = (ob + (1u << 20) - 1) & ~(size_t)((1u << 20) - 1);
+            if (hipMalloc((void **)&be->attn_stage, nbytes) != hipSuccess) {
+                (void)hipGetLastError();
+                return TTS_STATUS_ALLOC_FAILED;
+            }
+            be->attn_stage_size = nbytes;
+        }
+        launch_attn_bias(be, q, k, v, (const float *)it.bias->data, mask, it.scale, it.stage ? be->attn_stage : out, P, (int)it.q->ne[2],
+                         (int)it.q->ne[1]);
+        if (it.stage) TTS_HIP_CHECK(hipMemcpyAsync(out, be->attn_stage, ob, hipMemcpyDeviceToDevice, be->stream));
+        return 0;
+    }
     int64_t obs = -1, mbs = it.mask && it.mask->ne[3] > 1 ? (int64_t)(it.mask->nb[3] / 4) : 0;  // per-sequence masks
     if (const BatchCtx * bc = be->bat) {  // (co_prepare-checked: one sequence per member)
         batch_td(*bc, q);
@@ -2669,6 +2734,7 @@ static bool co_prepare(tts_hip_backend * be, Planner & pl, tts_tensor * const * 
                 break;
             }
             case Item::ATTN: {
+                if (it.bias) CO_NO();  // k_attn_bias takes one sequence
                 if (it.q->ne[3] != 1 || !inter(it.q) || !inter(it.out) || !equal_all(it.q) || !equal_all(it.out)) CO_NO();
                 if (it.mask && it.mask->ne[2] * it.mask->ne[3] != 1) CO_NO();
                 // each member's own key count; K [hd, P, Hk], V [P, hd, Hv] with the cache's strides

@@ -476,6 +476,8 @@ struct tts_hip_backend {
     char * repack_tmp = nullptr;  // device temp for Q4_K matrices not stored repacked
     size_t repack_tmp_size = 0;
     std::vector<char *> repack_retired;  // outgrown repack temps (freed with the backend)
+    float * attn_stage = nullptr;  // k_attn_bias' output when the graph's output tensor overlaps an operand (then copied to it)
+    size_t attn_stage_size = 0;
     // HIP graph replay of graph_compute (capture -> exec update -> one launch)
     bool use_graphs = false;
     // repeat detection for tts_hip_graph_compute: signatures of the last few graphs (node count, op

@@ -32,6 +32,9 @@ struct AttnArgs {
     const int64_t * voff = nullptr;
     const int64_t * moff = nullptr;
     const int * pseq = nullptr;
+    // k_attn_bias only: the tensor a graph adds to KQ before the softmax (T5's relative position
+    // bias), [P, n, H] contiguous f32
+    const float * bias = nullptr;
 };
 
 // per-sequence views of a ragged launch (AttnArgs::koff / voff / moff / pseq)
@@ -1198,6 +1201,88 @@ __global__ __launch_bounds__(64 * ATTN_SQ_WAVES) void k_attn_small_q(AttnArgs a)
 }
 
 // ------------------------------------------------------------------------------------------
+// Encoder attention with a per-head additive bias (the T5 voice-description encoder, t5/model.cpp:246-265):
+//   mul_mat(k, q) -> add(pos_bias) -> soft_max_ext(mask, scale) -> mul_mat(kq, v) -> permute(2,0,1,3) -> cont
+// hd = 64, P <= 512 keys, any number of queries, one sequence.  One workgroup serves a head and a
+// block of NW queries, one query per wave: K, then V, pass through one LDS tile in chunks of 64 keys
+// (rows padded to 65 floats: lane p reads K row p, lane d reads V row d, both conflict-free), so the
+// block reads K and V once; a wave's P scores stay in its LDS row between the two passes.  Every sum
+// is the oracle's, in its order: the dot product over d and the softmax denominator and the P.V sums
+// over the keys are sequential f64 chains, the bias is added to the f32-rounded dot product (the ADD
+// node's rounding).  Bit-identical to the unfused chain at every P.
+constexpr int ATTN_BIAS_MAXP = 512;
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void k_attn_bias(AttnArgs a) {
+    constexpr int HD = 64;
+    constexpr int TP = 65;  // floats per tile row: K [p][d], V [d][p]
+    __shared__ float st[64 * TP];
+    __shared__ float sp[NW][ATTN_BIAS_MAXP];
+    const int h = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int P = a.P;
+    const int tq0 = blockIdx.y * NW + wave;
+    const bool live = tq0 < a.n;
+    const int tq = live ? tq0 : a.n - 1;  // a wave past the last query repeats it and stores nothing (it still stages tiles)
+    const char * kbase = a.k.data + (int64_t)h * a.k.nb[2];
+    const char * vbase = a.v.data + (int64_t)h * a.v.nb[2];
+    const int64_t knb1 = a.k.nb[1], vnb0 = a.v.nb[0], vnb1 = a.v.nb[1];
+    // the query before anything is stored: the output may be the query's own memory, row for row
+    const float qv = *(const float *)(a.q.data + (int64_t)tq * a.q.nb[1] + (int64_t)h * a.q.nb[2] + (int64_t)lane * a.q.nb[0]);
+    const float * brow = a.bias + ((int64_t)h * a.n + tq) * P;
+    const float * mrow = a.mask ? a.mask + (int64_t)tq * P : nullptr;
+    float * row = sp[wave];
+    float mx = -INFINITY;
+    for (int c0 = 0; c0 < P; c0 += 64) {
+        const int cn = min(64, P - c0);
+        __syncthreads();
+        for (int i = tid; i < cn * HD; i += 64 * NW) {
+            const int p = i >> 6, d = i & 63;
+            st[p * TP + d] = *(const float *)(kbase + (int64_t)(c0 + p) * knb1 + 4 * d);
+        }
+        __syncthreads();
+        const int p = min(lane, cn - 1);
+        double acc = 0.0;
+#pragma unroll
+        for (int d = 0; d < HD; ++d)
+            acc += (double)__fmul_rn(st[p * TP + d], __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qv), d)));
+        float w = __fadd_rn((float)acc, brow[c0 + p]);
+        w = __fmul_rn(w, a.scale);
+        if (mrow) w = __fadd_rn(w, __fmul_rn(1.0f, mrow[c0 + p]));
+        if (lane < cn) {
+            row[c0 + lane] = w;
+            mx = fmaxf(mx, w);
+        }
+    }
+    for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    for (int i = lane; i < P; i += 64) row[i] = cr_expf(__fsub_rn(row[i], mx));
+    __syncthreads();
+    double sum = 0.0;
+#pragma unroll 8
+    for (int i = 0; i < P; ++i) sum += (double)row[i];
+    const float inv = (float)(1.0 / sum);
+    double o = 0.0;
+    for (int c0 = 0; c0 < P; c0 += 64) {
+        const int cn = min(64, P - c0);
+        __syncthreads();
+        if (vnb0 == 4) {  // positions contiguous in memory
+            for (int i = tid; i < cn * HD; i += 64 * NW) {
+                const int d = i / cn, p = i - d * cn;
+                st[d * TP + p] = *(const float *)(vbase + (int64_t)d * vnb1 + 4 * (int64_t)(c0 + p));
+            }
+        } else {  // dims contiguous (V read through the transpose of the projection output)
+            for (int i = tid; i < cn * HD; i += 64 * NW) {
+                const int p = i >> 6, d = i & 63;
+                st[d * TP + p] = *(const float *)(vbase + (int64_t)d * vnb1 + (int64_t)(c0 + p) * vnb0);
+            }
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int i = 0; i < cn; ++i) o += (double)__fmul_rn(__fmul_rn(row[c0 + i], inv), st[lane * TP + i]);
+    }
+    if (live) a.out[((int64_t)tq * a.H + h) * HD + lane] = (float)o;
+}
+
+// ------------------------------------------------------------------------------------------
 // KV prefetch into the memory-side Infinity Cache (MALL).  Decode attention streams the whole KV
 // cache of a layer once per step (Parler B = 8, P = 900: 59 MB); cold from HBM the row kernel
 // reaches about half the bandwidth it gets from MALL-resident data, while the GEMVs between two
@@ -1378,6 +1463,33 @@ void launch_attn_decode(tts_hip_backend * be, const TD & q, const TD & k, const 
         return;
     }
     hipLaunchKernelGGL(k_attn_decode, dim3((unsigned)H, (unsigned)n, (unsigned)B), dim3(ATTN_THREADS), 0, be->stream, a);
+    TTS_HIP_CHECK(hipGetLastError());
+}
+
+// Attention with an additive bias [P, n, H] (k_attn_bias): hd = 64, 1 <= P <= ATTN_BIAS_MAXP, one
+// sequence, K rows contiguous (the planner's conditions).  The query block is the workgroup's wave
+// count: 8, or 4 or 2 when 8 would leave fewer workgroups than CUs (T5 over a 32-token description with
+// 16 heads: 2 queries per workgroup = 256 workgroups).
+void launch_attn_bias(tts_hip_backend * be, const TD & q, const TD & k, const TD & v, const float * bias, const float * mask,
+                      float scale, float * out, int P, int H, int n) {
+    AttnArgs a;
+    a.q = q;
+    a.k = k;
+    a.v = v;
+    a.bias = bias;
+    a.mask = mask;
+    a.scale = scale;
+    a.out = out;
+    a.hd = 64;
+    a.P = P;
+    a.H = H;
+    a.n = n;
+    a.B = 1;
+    a.obs = (int64_t)n * H * 64;
+    const auto wgs = [&](int qb) { return (int64_t)H * ((n + qb - 1) / qb); };
+    if (wgs(8) >= be->cus) hipLaunchKernelGGL(k_attn_bias<8>, dim3((unsigned)H, (unsigned)((n + 7) / 8)), dim3(512), 0, be->stream, a);
+    else if (wgs(4) >= be->cus) hipLaunchKernelGGL(k_attn_bias<4>, dim3((unsigned)H, (unsigned)((n + 3) / 4)), dim3(256), 0, be->stream, a);
+    else hipLaunchKernelGGL(k_attn_bias<2>, dim3((unsigned)H, (unsigned)((n + 1) / 2)), dim3(128), 0, be->stream, a);
     TTS_HIP_CHECK(hipGetLastError());
 }
 

@@ -374,6 +374,18 @@ extern "C" void tts_parler_reset(tts_parler * p) {
     p->rep_count.assign((size_t)p->cfg.batch * p->cfg.n_output_heads, 0);
 }
 
+// parler_tts_runner::update_conditional_prompt (model.cpp:510-518): a new T5 encoding of the voice
+// description -> text_encoding, then prep_cross_key_values over it.  The cross caches and masks are
+// sized by n_encode, so n must equal it.
+extern "C" int tts_parler_set_conditional_prompt(tts_parler * p, const float * encoding, int32_t n) {
+    if (!p || !encoding || !p->cfg.use_cross_attn || n != p->cfg.n_encode) return TTS_STATUS_BAD_ARG;
+    if (p->be.synchronize(p->be.ctx) != 0) return TTS_STATUS_FAILED;  // no step in flight reads the old cross K / V
+    if (p->be.set_tensor(p->be.ctx, p->text_encoding, encoding) != 0) return TTS_STATUS_FAILED;
+    if (!prep_cross_key_values(p)) return TTS_STATUS_FAILED;
+    tts_parler_reset(p);
+    return TTS_STATUS_SUCCESS;
+}
+
 extern "C" void tts_parler_set_sampling(tts_parler * p, const tts_sampling * cfg) {
     p->sampling = cfg != nullptr;
     if (cfg) p->samp = *cfg;

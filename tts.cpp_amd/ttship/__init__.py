@@ -147,6 +147,27 @@ class ParlerConfig(ctypes.Structure):
     ]
 
 
+class T5Config(ctypes.Structure):
+    _fields_ = [
+        ("n_layers", ctypes.c_int32),
+        ("hidden_size", ctypes.c_int32),
+        ("n_attn_heads", ctypes.c_int32),
+        ("head_size", ctypes.c_int32),
+        ("ffn_size", ctypes.c_int32),
+        ("relative_attn_buckets", ctypes.c_int32),
+        ("vocab_size", ctypes.c_int32),
+        ("max_context_length", ctypes.c_int32),
+        ("output_size", ctypes.c_int32),
+        ("has_down_proj", ctypes.c_int32),
+        ("weight_type", ctypes.c_int32),
+        ("eos_token_id", ctypes.c_int32),
+        ("seed", ctypes.c_uint64),
+        ("arena_bytes", ctypes.c_uint64),
+        ("debug_no_reuse", ctypes.c_int32),
+        ("pad_", ctypes.c_int32),
+    ]
+
+
 class OrpheusConfig(ctypes.Structure):
     _fields_ = [
         ("n_layers", ctypes.c_int32),
@@ -380,6 +401,22 @@ def lib():
         "tts_orpheus_last_graph_nodes": (i32, [vp]),
         "tts_orpheus_weight_bytes": (u64, [vp]),
         "tts_orpheus_graph": (vp, [vp, ctypes.POINTER(i32)]),
+        "tts_t5_default_config": (None, [ctypes.POINTER(T5Config)]),
+        "tts_t5_create": (vp, [ctypes.POINTER(BackendIface), ctypes.POINTER(T5Config)]),
+        "tts_t5_free": (None, [vp]),
+        "tts_t5_encode": (ctypes.c_int, [vp, vp, i32, vp]),
+        "tts_t5_output_size": (i32, [vp]),
+        "tts_t5_last_graph_nodes": (i32, [vp]),
+        "tts_t5_weight_bytes": (u64, [vp]),
+        "tts_t5_n_weights": (i32, [vp]),
+        "tts_t5_weight": (u64, [vp, i32, ctypes.c_char_p, u64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(i32), vp, u64]),
+        "tts_t5_graph": (vp, [vp, ctypes.POINTER(i32)]),
+        "tts_t5_get_node": (u64, [vp, ctypes.c_char_p, vp, u64]),
+        "tts_t5_node": (u64, [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i64), vp, u64]),
+        "tts_t5_config_from_gguf": (ctypes.c_int, [vp, ctypes.POINTER(T5Config)]),
+        "tts_t5_create_from_gguf": (vp, [ctypes.POINTER(BackendIface), ctypes.POINTER(T5Config), vp]),
+        "tts_t5_write_synthetic_gguf": (ctypes.c_int, [ctypes.POINTER(T5Config), ctypes.c_char_p]),
+        "tts_parler_set_conditional_prompt": (ctypes.c_int, [vp, vp, i32]),
         "tts_parler_default_config": (None, [ctypes.POINTER(ParlerConfig)]),
         "tts_parler_create": (vp, [ctypes.POINTER(BackendIface), ctypes.POINTER(ParlerConfig)]),
         "tts_parler_free": (None, [vp]),
@@ -735,6 +772,89 @@ class Dia:
             self.ptr = None
 
 
+def t5_config(**kw):
+    cfg = T5Config()
+    lib().tts_t5_default_config(ctypes.byref(cfg))
+    for k, v in kw.items():
+        setattr(cfg, k, v)
+    return cfg
+
+
+class T5:
+    """T5 voice-description encoder runner (Parler's conditional prompt) over a backend vtable."""
+
+    def __init__(self, iface, cfg, gguf=None):
+        """gguf: a Gguf file whose "t5encoder.*" tensors are the weights (cfg from t5_config_from_gguf)."""
+        self.L = lib()
+        self.cfg = cfg
+        self._iface = iface
+        if gguf is None:
+            self.ptr = self.L.tts_t5_create(ctypes.byref(iface), ctypes.byref(cfg))
+        else:
+            self.ptr = self.L.tts_t5_create_from_gguf(ctypes.byref(iface), ctypes.byref(cfg), gguf.ptr)
+        if not self.ptr:
+            raise RuntimeError("tts_t5_create failed")
+
+    @classmethod
+    def from_gguf(cls, iface, g, **kw):
+        """A runner over the Gguf file g; kw overrides config fields the file does not carry (seed, arena_bytes)."""
+        return cls(iface, t5_config_from_gguf(g, **kw), gguf=g)
+
+    @property
+    def output_size(self):
+        return self.L.tts_t5_output_size(self.ptr)
+
+    def encode(self, tokens):
+        """tokens: ids with EOS already appended -> [n, output_size] float32."""
+        import numpy as np
+        tok = np.ascontiguousarray(tokens, dtype=np.int32).reshape(-1)
+        out = np.empty((tok.size, self.output_size), dtype=np.float32)
+        st = self.L.tts_t5_encode(self.ptr, tok.ctypes.data, tok.size, out.ctypes.data)
+        if st != 0:
+            raise RuntimeError(f"encode failed {st}")
+        return out
+
+    def last_graph_nodes(self):
+        return self.L.tts_t5_last_graph_nodes(self.ptr)
+
+    def weight_bytes(self):
+        return self.L.tts_t5_weight_bytes(self.ptr)
+
+    def weights(self):
+        return runner_weights(self.L.tts_t5_n_weights, self.L.tts_t5_weight, self.ptr)
+
+    def plan_stats(self, mask=None):
+        """Fusion coverage of the last encode graph (no device needed)."""
+        n = ctypes.c_int32()
+        p = self.L.tts_t5_graph(self.ptr, ctypes.byref(n))
+        return plan_stats(p, n.value, FUSE_ALL if mask is None else mask)
+
+    def node(self, i, cap=1 << 26):
+        """(op, type, ne, float32 array or None) of node i of the last graph (debugging)."""
+        import numpy as np
+        op, ty = ctypes.c_int32(), ctypes.c_int32()
+        ne = (ctypes.c_int64 * 4)()
+        buf = np.empty(cap // 4, dtype=np.float32)
+        n = self.L.tts_t5_node(self.ptr, i, ctypes.byref(op), ctypes.byref(ty), ne, buf.ctypes.data, cap)
+        data = buf[: n // 4].copy() if n else None
+        return OPS[op.value], ty.value, tuple(ne), data
+
+    def named(self, name, dtype="float32"):
+        """Flat values of a named tensor of the last graph ("pos_bucket" int32, "pos_bias", "t5_output"), or None."""
+        import numpy as np
+        n = self.L.tts_t5_get_node(self.ptr, name.encode(), None, 0)
+        if not n:
+            return None
+        a = np.empty(n // 4, dtype=dtype)
+        self.L.tts_t5_get_node(self.ptr, name.encode(), a.ctypes.data, n)
+        return a
+
+    def close(self):
+        if self.ptr:
+            self.L.tts_t5_free(self.ptr)
+            self.ptr = None
+
+
 def orpheus_config(**kw):
     cfg = OrpheusConfig()
     lib().tts_orpheus_default_config(ctypes.byref(cfg))
@@ -876,6 +996,18 @@ class Parler:
 
     def reset(self):
         self.L.tts_parler_reset(self.ptr)
+
+    def set_conditional_prompt(self, encoding):
+        """A new voice description (tts_parler_set_conditional_prompt): encoding [n_encode, hidden_size] float32, the
+        T5 encoder's output; recomputes the cross K / V and resets positions.  Raises ValueError when the
+        runner refuses it (n != cfg.n_encode, or no cross-attention) -- nothing has changed then."""
+        import numpy as np
+        e = np.ascontiguousarray(encoding, dtype=np.float32)
+        if e.ndim != 2 or e.shape[1] != self.cfg.hidden_size:
+            raise ValueError(f"encoding must be [n, {self.cfg.hidden_size}], got {e.shape}")
+        st = self.L.tts_parler_set_conditional_prompt(self.ptr, e.ctypes.data, e.shape[0])
+        if st != 0:
+            raise ValueError(f"set_conditional_prompt refused {e.shape[0]} tokens (n_encode {self.cfg.n_encode}): {st}")
 
     def set_device_sampling(self, on):
         """Greedy sampling on the device (default when the backend supports it) or on the host."""
@@ -1502,6 +1634,22 @@ def parler_config_from_gguf(g, **kw):
     for k, v in kw.items():  # caller overrides (batch, max_ctx, arena) win
         setattr(cfg, k, v)
     return cfg
+
+
+def t5_config_from_gguf(g, **kw):
+    cfg = t5_config(**kw)
+    if lib().tts_t5_config_from_gguf(g.ptr, ctypes.byref(cfg)) != 0:
+        raise RuntimeError("not a usable t5encoder GGUF file")
+    for k, v in kw.items():  # caller overrides (seed, arena) win
+        setattr(cfg, k, v)
+    return cfg
+
+
+def write_t5_synthetic_gguf(path, cfg):
+    """The T5 runner's synthetic weights for cfg as a GGUF file with the reference's names and keys."""
+    st = lib().tts_t5_write_synthetic_gguf(ctypes.byref(cfg), str(path).encode())
+    if st != 0:
+        raise RuntimeError(f"writing {path} failed {st}")
 
 
 def dac_config_from_gguf(g, **kw):

@@ -12,7 +12,7 @@
 
 #include "../../include/tts_gguf.h"
 #include "graph.h"
-#include "synth.h"
+#include "weights.h"
 #include "tts_hip.h"
 #include "tts_runners.h"
 
@@ -35,19 +35,12 @@ struct dac_quant {  // residual_vector_quantize_layer
     tts_tensor *codebook, *out_kernel, *out_bias;
 };
 
-struct wspec {
-    tts_tensor * t;
-    float scale, offset;
-    uint64_t seed;
-};
-
 }  // namespace
 
 struct tts_dac {
     tts_dac_config cfg;
     tts_backend_iface be;
-    tg::context wctx;
-    void * wbuf = nullptr;
+    weight_store w;  // the weights, declaration order
     std::vector<dac_quant> quant;
     tts_tensor *in_kernel = nullptr, *in_bias = nullptr, *out_alpha = nullptr, *out_kernel = nullptr, *out_bias = nullptr;
     tts_tensor * one = nullptr;  // the scalar 1.0 of reciprocal() (a device tensor, not a host static)
@@ -56,9 +49,6 @@ struct tts_dac {
     size_t arena_size = 0;
     tg::context gctx;
     tts_tensor * in_codes = nullptr;
-    uint64_t tensor_index = 0;
-    std::vector<wspec> specs;
-    const tts_gguf * gguf = nullptr;  // weight source while creating from a file (else synthetic)
     // batched decode (tts_dac_decode_batch): the prompt masks of the last (nb, T, gap), one per rate
     void * mask_buf = nullptr;
     size_t mask_bytes = 0;
@@ -81,12 +71,10 @@ extern "C" void tts_dac_default_config(tts_dac_config * c) {
     c->arena_bytes = 0;
 }
 
-static tts_tensor * wnew(tts_dac * d, float scale, float offset, int64_t ne0, int64_t ne1, int64_t ne2, const std::string & name) {
-    tts_tensor * t = tg::new_tensor_3d(d->wctx, TTS_TYPE_F32, ne0, ne1, ne2);
-    tg::set_name(t, name);
-    t->flags |= tg::TG_FLAG_PERSIST;
-    d->specs.push_back({t, scale, offset, d->cfg.seed ^ (d->tensor_index++)});
-    return t;
+// in_file = false: the runner's own constant, which no file holds
+static tts_tensor * wnew(tts_dac * d, float scale, float offset, int64_t ne0, int64_t ne1, int64_t ne2, const std::string & name,
+                         bool in_file = true) {
+    return d->w.add(TTS_TYPE_F32, ne0, ne1, ne2, name, weight_fill::uniform(scale, offset), d->cfg.seed ^ d->w.index(), in_file);
 }
 
 // conv kernel [K, IC, OC], uniform +-gain*sqrt(3/fan_in): gain 1 preserves the variance; the
@@ -96,59 +84,12 @@ static tts_tensor * conv_w(tts_dac * d, int K, int IC, int OC, const std::string
     return wnew(d, gain * std::sqrt(3.0f / (float)(K * IC)), 0.f, K, IC, OC, name);
 }
 
-// GGUF name of a weight: the reference's (dac_gguf_encoder.py's mapping, read back by
-// dac_model.cpp:58-98 / general_neural_audio_codec.cpp:36-127); the runner's own constant has none.
-static std::string gguf_name(const tts_tensor * t) { return std::string("audio_encoder.") + t->name; }
-
-static bool same_squeezed_shape(const int64_t * a, const int64_t * b) {
-    int64_t x[4], y[4];
-    int nx = 0, ny = 0;
-    for (int k = 0; k < 4; ++k) {
-        if (a[k] != 1) x[nx++] = a[k];
-        if (b[k] != 1) y[ny++] = b[k];
-    }
-    if (nx != ny) return false;
-    for (int k = 0; k < nx; ++k)
-        if (x[k] != y[k]) return false;
-    return true;
-}
-
-static bool upload(tts_dac * d) {
-    size_t total = 0;
-    for (auto & s : d->specs) total += (tg::nbytes(s.t) + 255) & ~(size_t)255;
-    d->wbuf = d->be.alloc(d->be.ctx, total);
-    if (!d->wbuf) return false;
-    size_t off = 0;
-    std::vector<float> host;
-    for (auto & s : d->specs) {
-        const size_t n = (size_t)tg::nelements(s.t);
-        s.t->data = (char *)d->wbuf + off;
-        off += (tg::nbytes(s.t) + 255) & ~(size_t)255;
-        const void * src = nullptr;
-        if (d->gguf && s.t != d->one) {  // assign_weight: the mapped file bytes
-            const std::string fname = gguf_name(s.t);
-            const int64_t i = tts_gguf_find_tensor(d->gguf, fname.c_str());
-            int64_t ne[4] = {1, 1, 1, 1};
-            if (i >= 0) tts_gguf_tensor_ndims(d->gguf, i, ne);
-            if (i < 0 || tts_gguf_tensor_type(d->gguf, i) != TTS_TYPE_F32 || !same_squeezed_shape(ne, s.t->ne)) {
-                fprintf(stderr, "gguf: DAC tensor '%s' %s (the decoder takes F32 [%lld %lld %lld])\n", fname.c_str(),
-                        i < 0 ? "is missing" : "has another type or shape", (long long)s.t->ne[0], (long long)s.t->ne[1], (long long)s.t->ne[2]);
-                return false;
-            }
-            src = tts_gguf_tensor_data(d->gguf, i);
-        } else {
-            host.resize(n);
-            synth_f32(host.data(), n, s.seed, s.scale, s.offset);
-            src = host.data();
-        }
-        if (d->be.set_tensor(d->be.ctx, s.t, src) != 0) return false;
-    }
-    return true;
-}
-
 // Declares every weight in the reference's order (synthetic seeds follow this order).
 static void declare_weights(tts_dac * d) {
     const auto & c = d->cfg;
+    // the reference's names (dac_gguf_encoder.py's mapping, read back by dac_model.cpp:58-98 /
+    // general_neural_audio_codec.cpp:36-127)
+    d->w.prefix = "audio_encoder.";
     for (int i = 0; i < c.n_codebooks; ++i) {
         dac_quant q;
         q.codebook = wnew(d, 1.0f, 0.f, c.codebook_dim, c.codebook_size, 1, "quantizers." + std::to_string(i) + ".codebook.weight");
@@ -186,17 +127,17 @@ static void declare_weights(tts_dac * d) {
     d->out_alpha = wnew(d, 0.5f, 1.0f, 1, ch, 1, "final.alpha");
     d->out_kernel = conv_w(d, 7, ch, 1, "final.weight", 0.3f);
     d->out_bias = wnew(d, 0.01f, 0.f, 1, 1, 1, "final.bias");
-    d->one = wnew(d, 0.f, 1.0f, 1, 1, 1, "one");
+    d->one = wnew(d, 0.f, 1.0f, 1, 1, 1, "one", false);
 }
 
 static tts_dac * dac_create(const tts_backend_iface * be, const tts_dac_config * cfg, const tts_gguf * g) {
     auto * d = new tts_dac();
     d->cfg = *cfg;
     d->be = *be;
-    d->gguf = g;
+    d->w.attach(g);
     const auto & c = d->cfg;
     declare_weights(d);
-    if (!upload(d)) {
+    if (!d->w.upload(d->be)) {
         tts_dac_free(d);
         return nullptr;
     }
@@ -211,7 +152,6 @@ static tts_dac * dac_create(const tts_backend_iface * be, const tts_dac_config *
         tts_dac_free(d);
         return nullptr;
     }
-    d->gguf = nullptr;
     return d;
 }
 
@@ -221,7 +161,7 @@ extern "C" void tts_dac_free(tts_dac * d) {
     if (!d) return;
     if (d->arena) d->be.free(d->be.ctx, d->arena);
     if (d->mask_buf) d->be.free(d->be.ctx, d->mask_buf);
-    if (d->wbuf) d->be.free(d->be.ctx, d->wbuf);
+    d->w.release(d->be);
     delete d;
 }
 
@@ -394,53 +334,36 @@ extern "C" int tts_dac_decode_batch(tts_dac * d, const int32_t * codes, int32_t 
 extern "C" int64_t tts_dac_min_gap(const tts_dac * d) { return d ? dac_min_gap(d) : 0; }
 
 extern "C" int32_t tts_dac_last_graph_nodes(const tts_dac * d) { return (int32_t)d->gctx.nodes.size(); }
-extern "C" int32_t tts_dac_n_weights(const tts_dac * d) { return d ? (int32_t)d->specs.size() : 0; }
+extern "C" int32_t tts_dac_n_weights(const tts_dac * d) { return d ? d->w.size() : 0; }
 extern "C" uint64_t tts_dac_weight(tts_dac * d, int32_t i, char * name, uint64_t name_cap, int64_t * ne, int32_t * type, void * dst,
                                    uint64_t cap) {
-    if (!d || i < 0 || i >= (int32_t)d->specs.size()) return 0;
-    return tg::weight_out(d->be, d->specs[i].t, name, name_cap, ne, type, dst, cap);
+    const tts_tensor * t = d ? d->w.tensor(i) : nullptr;
+    return t ? tg::weight_out(d->be, t, name, name_cap, ne, type, dst, cap) : 0;
 }
 
 extern "C" tts_tensor * const * tts_dac_graph(const tts_dac * d, int32_t * n_nodes) {
-    if (n_nodes) *n_nodes = d ? (int32_t)d->gctx.nodes.size() : 0;
-    return d ? d->gctx.nodes.data() : nullptr;
+    return tg::graph_out(d ? &d->gctx : nullptr, n_nodes);
 }
 
 // ---- GGUF loader path (dac_model::prep_constants / prep_layers / assign_weight) ----
-static bool key_u32(const tts_gguf * g, std::initializer_list<const char *> keys, uint32_t * out) {
-    for (const char * k : keys) {
-        const int64_t i = tts_gguf_find_key(g, k);
-        if (i >= 0 && tts_gguf_get_u32(g, i, out)) return true;
-    }
-    return false;
-}
-
-static int64_t tdim(const tts_gguf * g, const std::string & name, int k) {
-    const int64_t i = tts_gguf_find_tensor(g, name.c_str());
-    if (i < 0) return -1;
-    int64_t ne[4];
-    tts_gguf_tensor_ndims(g, i, ne);
-    return ne[k];
-}
-
 extern "C" int tts_dac_config_from_gguf(const tts_gguf * g, tts_dac_config * c) {
     if (!g || !c) return TTS_STATUS_BAD_ARG;
-    uint32_t v = 0;
-    if (key_u32(g, {"parler-tts.decoder.output_heads", "output_heads", "dia.decoder.output_heads"}, &v)) c->n_codebooks = (int32_t)v;
+    gguf_first_u32(g, {"parler-tts.decoder.output_heads", "output_heads", "dia.decoder.output_heads"}, &c->n_codebooks);
     int n_layers = 0;
     for (int l = 0; l < 8; ++l) {  // prep_layers: dac_layer_stride_{l} / dac_layer_padding_{l} per block
         const std::string sk = "dac_layer_stride_" + std::to_string(l), pk = "dac_layer_padding_" + std::to_string(l);
-        uint32_t s = 0, pd = 0;
-        if (!key_u32(g, {("dac." + sk).c_str(), sk.c_str()}, &s)) break;
-        if (!key_u32(g, {("dac." + pk).c_str(), pk.c_str()}, &pd)) {
+        int32_t s = 0, pd = 0;
+        if (!gguf_first_u32(g, {("dac." + sk).c_str(), sk.c_str()}, &s)) break;
+        if (!gguf_first_u32(g, {("dac." + pk).c_str(), pk.c_str()}, &pd)) {
             fprintf(stderr, "gguf: key %s must be specified for the DAC decoder\n", pk.c_str());
             return TTS_STATUS_BAD_ARG;
         }
-        if (pd != (s + 1) / 2) {
-            fprintf(stderr, "gguf: DAC block %d padding %u, the decoder assumes ceil(stride / 2) = %u\n", l, pd, (s + 1) / 2);
+        const uint32_t want = ((uint32_t)s + 1) / 2;  // the keys are u32
+        if ((uint32_t)pd != want) {
+            fprintf(stderr, "gguf: DAC block %d padding %u, the decoder assumes ceil(stride / 2) = %u\n", l, (uint32_t)pd, want);
             return TTS_STATUS_UNSUPPORTED;
         }
-        c->rates[l] = (int32_t)s;
+        c->rates[l] = s;
         n_layers = l + 1;
     }
     if (n_layers == 0) {
@@ -448,8 +371,9 @@ extern "C" int tts_dac_config_from_gguf(const tts_gguf * g, tts_dac_config * c) 
         return TTS_STATUS_BAD_ARG;
     }
     c->n_layers = n_layers;
-    const int64_t cd = tdim(g, "audio_encoder.quantizers.0.codebook.weight", 0), cs = tdim(g, "audio_encoder.quantizers.0.codebook.weight", 1);
-    const int64_t lat = tdim(g, "audio_encoder.initial.weight", 1), dd = tdim(g, "audio_encoder.initial.weight", 2);
+    const char * cbw = "audio_encoder.quantizers.0.codebook.weight";
+    const int64_t cd = gguf_tensor_dim(g, cbw, 0), cs = gguf_tensor_dim(g, cbw, 1);
+    const int64_t lat = gguf_tensor_dim(g, "audio_encoder.initial.weight", 1), dd = gguf_tensor_dim(g, "audio_encoder.initial.weight", 2);
     if (cd < 0 || cs < 0 || lat < 0 || dd < 0) {
         fprintf(stderr, "gguf: DAC tensors missing\n");
         return TTS_STATUS_BAD_ARG;
@@ -479,15 +403,6 @@ void dac_write_synthetic(const tts_dac_config * cfg, tts_gguf_writer * w) {
         tts_gguf_set_u32(w, ("dac.dac_layer_padding_" + std::to_string(l)).c_str(), (uint32_t)((cfg->rates[l] + 1) / 2));
     }
     tts_gguf_set_u32(w, "dac.up_scaling_factor", (uint32_t)hop);
-    std::vector<float> host;
-    for (auto & s : d.specs) {
-        if (s.t == d.one) continue;
-        const size_t n = (size_t)tg::nelements(s.t);
-        host.resize(n);
-        synth_f32(host.data(), n, s.seed, s.scale, s.offset);
-        int nd = 3;
-        while (nd > 1 && s.t->ne[nd - 1] == 1) --nd;
-        tts_gguf_add_tensor(w, gguf_name(s.t).c_str(), TTS_TYPE_F32, nd, s.t->ne, host.data(), n * 4);
-    }
+    d.w.write(w);
 }
 }  // namespace tts

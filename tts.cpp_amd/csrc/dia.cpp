@@ -14,7 +14,7 @@
 
 #include "../../include/tts_runners.h"
 #include "graph.h"
-#include "synth.h"
+#include "weights.h"
 
 using namespace tts;
 
@@ -30,15 +30,12 @@ struct dia_dec_layer {
 struct tts_dia {
     tts_dia_config cfg;
     tts_backend_iface be;
-    tg::context wctx;
-    void * wbuf = nullptr;
-    size_t wbytes = 0;
+    weight_store w;  // the weights (declaration order), and the caches' tensors in its context
     void * kvbuf = nullptr;
     tts_tensor *enc_embd = nullptr, *enc_norm = nullptr, *dec_norm = nullptr;
     std::vector<dia_enc_layer> enc;
     std::vector<dia_dec_layer> dec;
     std::vector<tts_tensor *> embds, heads;
-    std::vector<tts_tensor *> wlist;  // every weight, declaration order (tts_dia_weight)
     std::vector<tts_tensor *> k_l, v_l, cross_k_l, cross_v_l;
     char * arena = nullptr;
     size_t arena_size = 0;
@@ -84,37 +81,10 @@ extern "C" void tts_dia_default_config(tts_dia_config * c) {
     c->arena_bytes = 0;
 }
 
-static tts_tensor * wnew(tts_dia * p, std::vector<std::pair<tts_tensor *, int>> & specs, int type, int64_t ne0, int64_t ne1, int kind,
-                         const std::string & name) {
-    tts_tensor * t = ne1 > 1 ? tg::new_tensor_2d(p->wctx, type, ne0, ne1) : tg::new_tensor_1d(p->wctx, type, ne0);
-    tg::set_name(t, name);
-    t->flags |= tg::TG_FLAG_PERSIST;
-    specs.push_back({t, kind});
-    return t;
-}
-
-static bool upload_weights(tts_dia * p, std::vector<std::pair<tts_tensor *, int>> & specs) {
-    size_t total = 0;
-    for (auto & s : specs) total += (tg::nbytes(s.first) + 255) & ~(size_t)255;
-    p->wbuf = p->be.alloc(p->be.ctx, total);
-    if (!p->wbuf) return false;
-    p->wbytes = total;
-    size_t off = 0;
-    std::vector<char> host;
-    uint64_t idx = 0;
-    for (auto & s : specs) {
-        tts_tensor * t = s.first;
-        const uint64_t seed = p->cfg.seed ^ (idx++);
-        const size_t nb = tg::nbytes(t);
-        t->data = (char *)p->wbuf + off;
-        off += (nb + 255) & ~(size_t)255;
-        host.resize(nb);
-        const int64_t K = t->ne[0], rows = tg::nelements(t) / t->ne[0];
-        if (s.second == 1) synth_f32((float *)host.data(), (size_t)(K * rows), seed, 0.1f, 1.0f);  // norm weights ~1
-        else synth_fill(t->type, host.data(), rows, K, seed, s.second == 3 ? 0.25f : 0.02f);
-        if (p->be.set_tensor(p->be.ctx, t, host.data()) != 0) return false;
-    }
-    return true;
+// kind: 0 = matrix, 1 = norm weight (~1), 3 = embedding
+static tts_tensor * wnew(tts_dia * p, int type, int64_t ne0, int64_t ne1, int kind, const std::string & name) {
+    const weight_fill fill = kind == 1 ? weight_fill::uniform(0.1f, 1.0f) : weight_fill::matrix(kind == 3 ? 0.25f : 0.02f);
+    return p->w.add(type, ne0, ne1, 1, name, fill, p->cfg.seed ^ p->w.index());
 }
 
 extern "C" tts_dia * tts_dia_create(const tts_backend_iface * be, const tts_dia_config * cfg) {
@@ -125,49 +95,47 @@ extern "C" tts_dia * tts_dia_create(const tts_backend_iface * be, const tts_dia_
     const int64_t E = cf.encoder_hidden_size, D = cf.decoder_hidden_size, hd = cf.head_size;
     const int64_t EA = (int64_t)cf.encoder_attn_heads * hd, DA = (int64_t)cf.decoder_attn_heads * hd;
     const int64_t DKV = DA / cf.decoder_query_heads;
-    std::vector<std::pair<tts_tensor *, int>> specs;
-    p->enc_embd = wnew(p, specs, cf.weight_type, E, cf.encoder_vocab_size, 3, "encoder.embedding");
+    p->enc_embd = wnew(p, cf.weight_type, E, cf.encoder_vocab_size, 3, "encoder.embedding");
     p->enc.resize(cf.n_encoder_layers);
     for (int l = 0; l < cf.n_encoder_layers; ++l) {
         auto & L = p->enc[l];
         const std::string pre = "encoder.layers." + std::to_string(l);
-        L.self_attn_norm = wnew(p, specs, TTS_TYPE_F32, E, 1, 1, pre + ".self_attn_norm");
-        L.q = wnew(p, specs, cf.weight_type, E, EA, 0, pre + ".q");
-        L.k = wnew(p, specs, cf.weight_type, E, EA, 0, pre + ".k");
-        L.v = wnew(p, specs, cf.weight_type, E, EA, 0, pre + ".v");
-        L.o = wnew(p, specs, cf.weight_type, EA, E, 0, pre + ".o");
-        L.mlp_norm = wnew(p, specs, TTS_TYPE_F32, E, 1, 1, pre + ".mlp_norm");
-        L.gate = wnew(p, specs, cf.weight_type, E, cf.encoder_ffn_size, 0, pre + ".gate");
-        L.up = wnew(p, specs, cf.weight_type, E, cf.encoder_ffn_size, 0, pre + ".up");
-        L.out = wnew(p, specs, cf.weight_type, cf.encoder_ffn_size, E, 0, pre + ".out");
+        L.self_attn_norm = wnew(p, TTS_TYPE_F32, E, 1, 1, pre + ".self_attn_norm");
+        L.q = wnew(p, cf.weight_type, E, EA, 0, pre + ".q");
+        L.k = wnew(p, cf.weight_type, E, EA, 0, pre + ".k");
+        L.v = wnew(p, cf.weight_type, E, EA, 0, pre + ".v");
+        L.o = wnew(p, cf.weight_type, EA, E, 0, pre + ".o");
+        L.mlp_norm = wnew(p, TTS_TYPE_F32, E, 1, 1, pre + ".mlp_norm");
+        L.gate = wnew(p, cf.weight_type, E, cf.encoder_ffn_size, 0, pre + ".gate");
+        L.up = wnew(p, cf.weight_type, E, cf.encoder_ffn_size, 0, pre + ".up");
+        L.out = wnew(p, cf.weight_type, cf.encoder_ffn_size, E, 0, pre + ".out");
     }
-    p->enc_norm = wnew(p, specs, TTS_TYPE_F32, E, 1, 1, "encoder.norm");
+    p->enc_norm = wnew(p, TTS_TYPE_F32, E, 1, 1, "encoder.norm");
     for (int i = 0; i < cf.n_output_heads; ++i)
-        p->embds.push_back(wnew(p, specs, cf.weight_type, D, cf.output_vocab_size, 3, "decoder.embds." + std::to_string(i)));
+        p->embds.push_back(wnew(p, cf.weight_type, D, cf.output_vocab_size, 3, "decoder.embds." + std::to_string(i)));
     p->dec.resize(cf.n_decoder_layers);
     for (int l = 0; l < cf.n_decoder_layers; ++l) {
         auto & L = p->dec[l];
         const std::string pre = "decoder.layers." + std::to_string(l);
-        L.self_attn_norm = wnew(p, specs, TTS_TYPE_F32, D, 1, 1, pre + ".self_attn_norm");
-        L.q = wnew(p, specs, cf.weight_type, D, DA, 0, pre + ".self_attn_q");
-        L.k = wnew(p, specs, cf.weight_type, D, DKV, 0, pre + ".self_attn_k");
-        L.v = wnew(p, specs, cf.weight_type, D, DKV, 0, pre + ".self_attn_v");
-        L.o = wnew(p, specs, cf.weight_type, DA, D, 0, pre + ".self_attn_o");
-        L.cross_attn_norm = wnew(p, specs, TTS_TYPE_F32, D, 1, 1, pre + ".cross_attn_norm");
-        L.cq = wnew(p, specs, cf.weight_type, D, DA, 0, pre + ".cross_attn_q");
-        L.ck = wnew(p, specs, cf.weight_type, E, DA, 0, pre + ".cross_attn_k");
-        L.cv = wnew(p, specs, cf.weight_type, E, DA, 0, pre + ".cross_attn_v");
-        L.co = wnew(p, specs, cf.weight_type, DA, D, 0, pre + ".cross_attn_o");
-        L.mlp_norm = wnew(p, specs, TTS_TYPE_F32, D, 1, 1, pre + ".mlp_norm");
-        L.gate = wnew(p, specs, cf.weight_type, D, cf.decoder_ffn_size, 0, pre + ".gate");
-        L.up = wnew(p, specs, cf.weight_type, D, cf.decoder_ffn_size, 0, pre + ".up");
-        L.out = wnew(p, specs, cf.weight_type, cf.decoder_ffn_size, D, 0, pre + ".out");
+        L.self_attn_norm = wnew(p, TTS_TYPE_F32, D, 1, 1, pre + ".self_attn_norm");
+        L.q = wnew(p, cf.weight_type, D, DA, 0, pre + ".self_attn_q");
+        L.k = wnew(p, cf.weight_type, D, DKV, 0, pre + ".self_attn_k");
+        L.v = wnew(p, cf.weight_type, D, DKV, 0, pre + ".self_attn_v");
+        L.o = wnew(p, cf.weight_type, DA, D, 0, pre + ".self_attn_o");
+        L.cross_attn_norm = wnew(p, TTS_TYPE_F32, D, 1, 1, pre + ".cross_attn_norm");
+        L.cq = wnew(p, cf.weight_type, D, DA, 0, pre + ".cross_attn_q");
+        L.ck = wnew(p, cf.weight_type, E, DA, 0, pre + ".cross_attn_k");
+        L.cv = wnew(p, cf.weight_type, E, DA, 0, pre + ".cross_attn_v");
+        L.co = wnew(p, cf.weight_type, DA, D, 0, pre + ".cross_attn_o");
+        L.mlp_norm = wnew(p, TTS_TYPE_F32, D, 1, 1, pre + ".mlp_norm");
+        L.gate = wnew(p, cf.weight_type, D, cf.decoder_ffn_size, 0, pre + ".gate");
+        L.up = wnew(p, cf.weight_type, D, cf.decoder_ffn_size, 0, pre + ".up");
+        L.out = wnew(p, cf.weight_type, cf.decoder_ffn_size, D, 0, pre + ".out");
     }
-    p->dec_norm = wnew(p, specs, TTS_TYPE_F32, D, 1, 1, "decoder.norm");
+    p->dec_norm = wnew(p, TTS_TYPE_F32, D, 1, 1, "decoder.norm");
     for (int i = 0; i < cf.n_output_heads; ++i)
-        p->heads.push_back(wnew(p, specs, cf.head_type, D, cf.output_vocab_size, 0, "decoder.heads." + std::to_string(i)));
-    for (auto & s : specs) p->wlist.push_back(s.first);
-    if (!upload_weights(p, specs)) {
+        p->heads.push_back(wnew(p, cf.head_type, D, cf.output_vocab_size, 0, "decoder.heads." + std::to_string(i)));
+    if (!p->w.upload(p->be)) {
         fprintf(stderr, "dia: weight allocation/upload failed\n");
         tts_dia_free(p);
         return nullptr;
@@ -185,13 +153,13 @@ extern "C" tts_dia * tts_dia_create(const tts_backend_iface * be, const tts_dia_
     char * kp = (char *)p->kvbuf;
     for (int l = 0; l < cf.n_decoder_layers; ++l) {
         tts_tensor * t;
-        t = tg::new_tensor_1d(p->wctx, TTS_TYPE_F32, DA * cf.max_generation_size * 2);
+        t = tg::new_tensor_1d(p->w.wctx, TTS_TYPE_F32, DA * cf.max_generation_size * 2);
         t->data = kp, kp += selfb, p->k_l.push_back(t);
-        t = tg::new_tensor_1d(p->wctx, TTS_TYPE_F32, DA * cf.max_generation_size * 2);
+        t = tg::new_tensor_1d(p->w.wctx, TTS_TYPE_F32, DA * cf.max_generation_size * 2);
         t->data = kp, kp += selfb, p->v_l.push_back(t);
-        t = tg::new_tensor_4d(p->wctx, TTS_TYPE_F32, hd, cf.decoder_attn_heads, 2, cf.max_encoder_context_length);
+        t = tg::new_tensor_4d(p->w.wctx, TTS_TYPE_F32, hd, cf.decoder_attn_heads, 2, cf.max_encoder_context_length);
         t->data = kp, kp += crossb, p->cross_k_l.push_back(t);
-        t = tg::new_tensor_4d(p->wctx, TTS_TYPE_F32, cf.max_encoder_context_length, hd, cf.decoder_attn_heads, 2);
+        t = tg::new_tensor_4d(p->w.wctx, TTS_TYPE_F32, cf.max_encoder_context_length, hd, cf.decoder_attn_heads, 2);
         t->data = kp, kp += crossb, p->cross_v_l.push_back(t);
     }
     p->arena_size = cf.arena_bytes ? cf.arena_bytes : (2ull << 30);
@@ -207,7 +175,7 @@ extern "C" void tts_dia_free(tts_dia * p) {
     if (!p) return;
     if (p->arena) p->be.free(p->be.ctx, p->arena);
     if (p->kvbuf) p->be.free(p->be.ctx, p->kvbuf);
-    if (p->wbuf) p->be.free(p->be.ctx, p->wbuf);
+    p->w.release(p->be);
     delete p;
 }
 
@@ -537,14 +505,13 @@ extern "C" int tts_dia_generate(tts_dia * p, const int32_t * first_audio, int32_
 
 extern "C" int32_t tts_dia_position(const tts_dia * p) { return p->position; }
 extern "C" int32_t tts_dia_last_graph_nodes(const tts_dia * p) { return p->last_nodes; }
-extern "C" uint64_t tts_dia_weight_bytes(const tts_dia * p) { return p->wbytes; }
-extern "C" int32_t tts_dia_n_weights(const tts_dia * p) { return p ? (int32_t)p->wlist.size() : 0; }
+extern "C" uint64_t tts_dia_weight_bytes(const tts_dia * p) { return p->w.wbytes; }
+extern "C" int32_t tts_dia_n_weights(const tts_dia * p) { return p ? p->w.size() : 0; }
 extern "C" uint64_t tts_dia_weight(tts_dia * p, int32_t i, char * name, uint64_t name_cap, int64_t * ne, int32_t * type, void * dst,
                                    uint64_t cap) {
-    if (!p || i < 0 || i >= (int32_t)p->wlist.size()) return 0;
-    return tg::weight_out(p->be, p->wlist[i], name, name_cap, ne, type, dst, cap);
+    const tts_tensor * t = p ? p->w.tensor(i) : nullptr;
+    return t ? tg::weight_out(p->be, t, name, name_cap, ne, type, dst, cap) : 0;
 }
 extern "C" tts_tensor * const * tts_dia_graph(const tts_dia * p, int32_t * n_nodes) {
-    if (n_nodes) *n_nodes = p ? (int32_t)p->gctx.nodes.size() : 0;
-    return p ? p->gctx.nodes.data() : nullptr;
+    return tg::graph_out(p ? &p->gctx : nullptr, n_nodes);
 }

@@ -619,4 +619,33 @@ uint64_t weight_out(const tts_backend_iface & be, const tts_tensor * t, char * n
     return n;
 }
 
+uint64_t tensor_out(const tts_backend_iface & be, const tts_tensor * t, void * dst, uint64_t cap) {
+    if (!is_contiguous(t)) return 0;
+    const uint64_t n = nbytes(t);
+    if (dst && cap >= n && be.get(be.ctx, dst, t->data, n) != 0) return 0;
+    return n;
+}
+
+uint64_t named_node_out(const tts_backend_iface & be, const std::vector<tts_tensor *> & nodes, const char * name, void * dst, uint64_t cap) {
+    for (const tts_tensor * t : nodes)
+        if (strcmp(t->name, name) == 0 && is_contiguous(t)) return tensor_out(be, t, dst, cap);
+    return 0;
+}
+
+uint64_t node_out(const tts_backend_iface & be, const std::vector<tts_tensor *> & nodes, int32_t i, int32_t * op, int32_t * type,
+                  int64_t * ne, void * dst, uint64_t cap) {
+    if (i < 0 || i >= (int32_t)nodes.size()) return 0;
+    const tts_tensor * t = nodes[i];
+    *op = t->op;
+    *type = t->type;
+    for (int k = 0; k < 4; ++k) ne[k] = t->ne[k];
+    if (!dst || nbytes(t) > cap) return 0;
+    return tensor_out(be, t, dst, cap);
+}
+
+tts_tensor * const * graph_out(const context * c, int32_t * n_nodes) {
+    if (n_nodes) *n_nodes = c ? (int32_t)c->nodes.size() : 0;
+    return c ? c->nodes.data() : nullptr;
+}
+
 }  // namespace tg

@@ -117,4 +117,15 @@ bool alloc_graph(context & c, char * arena_base, size_t arena_size, bool reuse =
 // backend stores them (F32 / F16 as ggml's; quantized types in the backend's layout).  Returns the size.
 uint64_t weight_out(const tts_backend_iface & be, const tts_tensor * t, char * name, uint64_t name_cap, int64_t * ne, int32_t * type,
                     void * dst, uint64_t cap);
+// The debug getters of the runners (tts_*_get_node, tts_*_node, tts_*_graph) over a graph's node list.
+// A contiguous tensor's bytes into dst when dst is given and cap suffices; returns their size (a size
+// query with dst == NULL), 0 for a non-contiguous tensor or a failed read.
+uint64_t tensor_out(const tts_backend_iface & be, const tts_tensor * t, void * dst, uint64_t cap);
+// tensor_out of the first contiguous node called `name`; 0 when there is none.
+uint64_t named_node_out(const tts_backend_iface & be, const std::vector<tts_tensor *> & nodes, const char * name, void * dst, uint64_t cap);
+// Node i -> op, type, ne[4], and its bytes if it is contiguous, dst is given and cap suffices (else returns 0).
+uint64_t node_out(const tts_backend_iface & be, const std::vector<tts_tensor *> & nodes, int32_t i, int32_t * op, int32_t * type,
+                  int64_t * ne, void * dst, uint64_t cap);
+// The node array of c (NULL: none) and its length, e.g. for tts_hip_plan_stats.
+tts_tensor * const * graph_out(const context * c, int32_t * n_nodes);
 }  // namespace tg

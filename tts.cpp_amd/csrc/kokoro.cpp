@@ -17,7 +17,7 @@
 #include "graph.h"
 #include "common.h"
 #include "kokoro_gen.h"
-#include "synth.h"
+#include "weights.h"
 #include "tts_hip.h"
 #include "tts_runners.h"
 
@@ -41,12 +41,6 @@ struct kk_up {  // kokoro_generator_upsample_block + its kokoro_noise_residual_b
     kk_res nres;
 };
 
-struct wspec {
-    tts_tensor * t;
-    float scale, offset;
-    uint64_t seed;
-};
-
 constexpr int kUpsample = 300;  // build_sin_gen's fixed interpolation factor (model.cpp:175, :196)
 
 }  // namespace
@@ -54,10 +48,7 @@ constexpr int kUpsample = 300;  // build_sin_gen's fixed interpolation factor (m
 struct tts_kokoro_gen {
     tts_kokoro_gen_config cfg;
     tts_backend_iface be;
-    tg::context wctx;
-    void * wbuf = nullptr;
-    std::vector<wspec> specs;
-    uint64_t tensor_index = 0;
+    weight_store w;  // the weights, declaration order
     std::vector<kk_up> ups;
     std::vector<kk_res> res;  // n_ups * n_kernels
     tts_tensor *m_w = nullptr, *m_b = nullptr, *out_w = nullptr, *out_b = nullptr;
@@ -99,11 +90,7 @@ extern "C" void tts_kokoro_gen_default_config(tts_kokoro_gen_config * c) {
 static tts_tensor * wnew(tts_kokoro_gen * k, float scale, float offset, int64_t ne0, int64_t ne1, int64_t ne2, const std::string & name,
                          bool gguf = true) {
     const int ty = gguf && k->cfg.weight_type == TTS_TYPE_F16 && kokoro_f16_tensor(name, ne1) ? TTS_TYPE_F16 : TTS_TYPE_F32;
-    tts_tensor * t = ne1 == 0 ? tg::new_tensor_1d(k->wctx, ty, ne0) : tg::new_tensor_3d(k->wctx, ty, ne0, ne1, ne2);
-    tg::set_name(t, name);
-    t->flags |= tg::TG_FLAG_PERSIST;
-    k->specs.push_back({t, scale, offset, k->cfg.seed ^ (k->tensor_index++)});
-    return t;
+    return k->w.add(ty, ne0, ne1, ne2, name, weight_fill::uniform(scale, offset), k->cfg.seed ^ k->w.index(), gguf);
 }
 
 // conv kernel [K, IC, OC], uniform +-gain*sqrt(3/fan_in)
@@ -141,32 +128,7 @@ static int64_t upsample_total(const tts_kokoro_gen_config & c) {
     return u;
 }
 
-static bool upload(tts_kokoro_gen * k) {
-    size_t total = 0;
-    for (auto & s : k->specs) total += (tg::nbytes(s.t) + 255) & ~(size_t)255;
-    k->wbuf = k->be.alloc(k->be.ctx, total);
-    if (!k->wbuf) return false;
-    size_t off = 0;
-    std::vector<float> host;
-    for (auto & s : k->specs) {
-        const size_t n = (size_t)tg::nelements(s.t);
-        s.t->data = (char *)k->wbuf + off;
-        off += (tg::nbytes(s.t) + 255) & ~(size_t)255;
-        host.resize(n);
-        synth_f32(host.data(), n, s.seed, s.scale, s.offset);
-        if (!kokoro_upload_weight(k->be, s.t, host.data(), n)) return false;
-    }
-    return true;
-}
-
 namespace tts {
-bool kokoro_upload_weight(const tts_backend_iface & be, tts_tensor * t, const float * host, size_t n) {
-    if (t->type != TTS_TYPE_F16) return be.set_tensor(be.ctx, t, host) == 0;
-    std::vector<uint16_t> h(n);
-    for (size_t i = 0; i < n; ++i) h[i] = fp32_to_fp16_host(host[i]);
-    return be.set_tensor(be.ctx, t, h.data()) == 0;
-}
-
 // f32 values of a weight (F16 weights widened), for the tests' float references
 uint64_t kokoro_read_weight(const tts_backend_iface & be, const tts_tensor * t, float * dst, uint64_t cap) {
     const uint64_t n = (uint64_t)tg::nelements(t) * 4;
@@ -231,7 +193,7 @@ extern "C" tts_kokoro_gen * tts_kokoro_gen_create(const tts_backend_iface * be, 
     k->samp_scalar = wnew(k, 0.f, 0.f, 1, 0, 0, "sampling_factor_scalar", false);
     k->nker = wnew(k, 0.f, 0.f, 1, 0, 0, "n_kernels_tensor", false);
     k->one = wnew(k, 0.f, 1.0f, 1, 1, 1, "one", false);
-    if (!upload(k)) {
+    if (!k->w.upload(k->be)) {
         tts_kokoro_gen_free(k);
         return nullptr;
     }
@@ -264,7 +226,7 @@ extern "C" tts_kokoro_gen * tts_kokoro_gen_create(const tts_backend_iface * be, 
 extern "C" void tts_kokoro_gen_free(tts_kokoro_gen * k) {
     if (!k) return;
     if (k->arena) k->be.free(k->be.ctx, k->arena);
-    if (k->wbuf) k->be.free(k->be.ctx, k->wbuf);
+    k->w.release(k->be);
     delete k;
 }
 
@@ -449,49 +411,28 @@ extern "C" int tts_kokoro_gen_run(tts_kokoro_gen * k, const float * x, const flo
 
 extern "C" int32_t tts_kokoro_gen_last_graph_nodes(const tts_kokoro_gen * k) { return (int32_t)k->gctx.nodes.size(); }
 
-extern "C" int32_t tts_kokoro_gen_n_weights(const tts_kokoro_gen * k) { return (int32_t)k->specs.size(); }
+extern "C" int32_t tts_kokoro_gen_n_weights(const tts_kokoro_gen * k) { return k->w.size(); }
 
 // Weight i: name, ne[4] and (when dst is non-null and cap suffices) its f32 values; returns bytes.
 extern "C" uint64_t tts_kokoro_gen_weight(tts_kokoro_gen * k, int32_t i, char * name, uint64_t name_cap, int64_t * ne, float * dst,
                                           uint64_t cap) {
-    if (!k || i < 0 || i >= (int32_t)k->specs.size()) return 0;
-    const tts_tensor * t = k->specs[i].t;
-    if (name && name_cap) {
-        strncpy(name, t->name, name_cap - 1);
-        name[name_cap - 1] = 0;
-    }
-    if (ne)
-        for (int d = 0; d < 4; ++d) ne[d] = t->ne[d];
+    const tts_tensor * t = k ? k->w.tensor(i) : nullptr;
+    if (!t) return 0;
+    tg::weight_out(k->be, t, name, name_cap, ne, nullptr, nullptr, 0);
     return kokoro_read_weight(k->be, t, dst, cap);
 }
 
 // Debug: copy the named node of the last graph to host (contiguous nodes only); returns bytes.
 extern "C" uint64_t tts_kokoro_gen_get_node(tts_kokoro_gen * k, const char * name, void * dst, uint64_t cap) {
-    if (!k || !name) return 0;
-    for (tts_tensor * t : k->gctx.nodes) {
-        if (strcmp(t->name, name) != 0 || !tg::is_contiguous(t)) continue;
-        const uint64_t n = tg::nbytes(t);
-        if (dst && cap >= n && k->be.get(k->be.ctx, dst, t->data, n) != 0) return 0;
-        return n;
-    }
-    return 0;
+    return k && name ? tg::named_node_out(k->be, k->gctx.nodes, name, dst, cap) : 0;
 }
 
 // Debug: node i of the last graph: op / type / ne; copies its bytes when contiguous (returns size).
 extern "C" uint64_t tts_kokoro_gen_node(tts_kokoro_gen * k, int32_t i, int32_t * op, int32_t * type, int64_t * ne, void * dst, uint64_t cap) {
-    if (!k || i < 0 || i >= (int32_t)k->gctx.nodes.size()) return 0;
-    const tts_tensor * t = k->gctx.nodes[i];
-    *op = t->op;
-    *type = t->type;
-    for (int d = 0; d < 4; ++d) ne[d] = t->ne[d];
-    if (!tg::is_contiguous(t) || !dst) return 0;
-    const uint64_t n = tg::nbytes(t);
-    if (n > cap || k->be.get(k->be.ctx, dst, t->data, n) != 0) return 0;
-    return n;
+    return k ? tg::node_out(k->be, k->gctx.nodes, i, op, type, ne, dst, cap) : 0;
 }
 
 // The last graph's node list (valid until the next run), e.g. for tts_hip_plan_stats.
 extern "C" tts_tensor * const * tts_kokoro_gen_graph(const tts_kokoro_gen * k, int32_t * n_nodes) {
-    if (n_nodes) *n_nodes = k ? (int32_t)k->gctx.nodes.size() : 0;
-    return k ? k->gctx.nodes.data() : nullptr;
+    return tg::graph_out(k ? &k->gctx : nullptr, n_nodes);
 }

@@ -38,8 +38,6 @@ inline bool kokoro_f16_tensor(const std::string & name, int64_t ne1) {
            !ends("norm");
 }
 
-// Host upload of one synthetic weight as its tensor type (F32, or F16 rounded to nearest even).
-bool kokoro_upload_weight(const tts_backend_iface & be, tts_tensor * t, const float * host, size_t n);
 // f32 values of a weight (F16 widened) into dst; returns nelements * 4 (0 on a failed read)
 uint64_t kokoro_read_weight(const tts_backend_iface & be, const tts_tensor * t, float * dst, uint64_t cap);
 

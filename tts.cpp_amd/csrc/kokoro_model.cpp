@@ -28,19 +28,13 @@
 
 #include "graph.h"
 #include "kokoro_gen.h"
-#include "synth.h"
+#include "weights.h"
 #include "tts_hip.h"
 #include "tts_runners.h"
 
 using namespace tts;
 
 namespace {
-
-struct wspec {
-    tts_tensor * t;
-    float scale, offset;
-    uint64_t seed;
-};
 
 struct kk_lstm {  // lstm / lstm_cell (model.h): one cell, optionally bidirectional
     tts_tensor *w[8], *b[8], *rw[8], *rb[8];
@@ -73,10 +67,7 @@ struct tts_kokoro {
     tts_kokoro_config cfg;
     tts_backend_iface be;
     tts_kokoro_gen * gen = nullptr;
-    tg::context wctx;
-    void * wbuf = nullptr;
-    std::vector<wspec> specs;
-    uint64_t tensor_index = 0;
+    weight_store w;  // the weights, declaration order
     // ALBERT
     tts_tensor *tok_embd, *pos_embd, *tt_values, *in_nw, *in_nb, *embd_hidden, *embd_hidden_b;
     std::vector<kk_albert_layer> layers;
@@ -135,13 +126,7 @@ extern "C" void tts_kokoro_default_config(tts_kokoro_config * c) {
 static tts_tensor * wnew(tts_kokoro * k, float scale, float offset, int64_t ne0, int64_t ne1, int64_t ne2, const std::string & name,
                          bool gguf = true) {
     const int ty = gguf && k->cfg.weight_type == TTS_TYPE_F16 && kokoro_f16_tensor(name, ne1) ? TTS_TYPE_F16 : TTS_TYPE_F32;
-    tts_tensor * t = ne1 == 0 ? tg::new_tensor_1d(k->wctx, ty, ne0)
-                   : ne2 == 0 ? tg::new_tensor_2d(k->wctx, ty, ne0, ne1)
-                              : tg::new_tensor_3d(k->wctx, ty, ne0, ne1, ne2);
-    tg::set_name(t, name);
-    t->flags |= tg::TG_FLAG_PERSIST;
-    k->specs.push_back({t, scale, offset, k->cfg.seed ^ (k->tensor_index++ * 0x9E3779B97F4A7C15ull)});
-    return t;
+    return k->w.add(ty, ne0, ne1, ne2, name, weight_fill::uniform(scale, offset), k->cfg.seed ^ (k->w.index() * 0x9E3779B97F4A7C15ull), gguf);
 }
 
 // Linear(in -> out) as ggml holds it: [in, out], uniform +-gain*sqrt(3/in)
@@ -194,24 +179,6 @@ static kk_ada make_ada(tts_kokoro * k, int cin, int cout, bool upsample, const s
     }
     if (cin != cout) a.up = lin(k, cin, cout, pre + ".conv1x1_weight");  // squeeze_3d_2d_e0'd [1, cin, cout]
     return a;
-}
-
-static bool upload(tts_kokoro * k) {
-    size_t total = 0;
-    for (auto & s : k->specs) total += (tg::nbytes(s.t) + 255) & ~(size_t)255;
-    k->wbuf = k->be.alloc(k->be.ctx, total);
-    if (!k->wbuf) return false;
-    size_t off = 0;
-    std::vector<float> host;
-    for (auto & s : k->specs) {
-        const size_t n = (size_t)tg::nelements(s.t);
-        s.t->data = (char *)k->wbuf + off;
-        off += (tg::nbytes(s.t) + 255) & ~(size_t)255;
-        host.resize(n);
-        synth_f32(host.data(), n, s.seed, s.scale, s.offset);
-        if (!kokoro_upload_weight(k->be, s.t, host.data(), n)) return false;
-    }
-    return true;
 }
 
 extern "C" tts_kokoro * tts_kokoro_create(const tts_backend_iface * be, const tts_kokoro_config * cfg) {
@@ -317,7 +284,7 @@ extern "C" tts_kokoro * tts_kokoro_create(const tts_backend_iface * be, const tt
     }
     k->voice = wnew(k, 0.5f, 0.f, 2 * S, c.n_voice_rows, 0, "voice_tensors.synthetic");
     k->sqrt2 = wnew(k, 0.f, (float)std::sqrt(2.0), 1, 0, 0, "sqrt_tensor", false);
-    if (!upload(k)) {
+    if (!k->w.upload(k->be)) {
         tts_kokoro_free(k);
         return nullptr;
     }
@@ -344,7 +311,7 @@ extern "C" tts_kokoro * tts_kokoro_create(const tts_backend_iface * be, const tt
 extern "C" void tts_kokoro_free(tts_kokoro * k) {
     if (!k) return;
     if (k->arena) k->be.free(k->be.ctx, k->arena);
-    if (k->wbuf) k->be.free(k->be.ctx, k->wbuf);
+    k->w.release(k->be);
     tts_kokoro_gen_free(k->gen);
     delete k;
 }
@@ -692,35 +659,21 @@ extern "C" int32_t tts_kokoro_last_graph_nodes(const tts_kokoro * k, int32_t whi
 }
 
 extern "C" int32_t tts_kokoro_n_weights(const tts_kokoro * k) {
-    return k ? (int32_t)k->specs.size() + tts_kokoro_gen_n_weights(k->gen) : 0;
+    return k ? k->w.size() + tts_kokoro_gen_n_weights(k->gen) : 0;
 }
 
 extern "C" uint64_t tts_kokoro_weight(tts_kokoro * k, int32_t i, char * name, uint64_t name_cap, int64_t * ne, float * dst, uint64_t cap) {
     if (!k || i < 0) return 0;
-    if (i >= (int32_t)k->specs.size()) return tts_kokoro_gen_weight(k->gen, i - (int32_t)k->specs.size(), name, name_cap, ne, dst, cap);
-    const tts_tensor * t = k->specs[i].t;
-    if (name && name_cap) {
-        strncpy(name, t->name, name_cap - 1);
-        name[name_cap - 1] = 0;
-    }
-    if (ne)
-        for (int d = 0; d < 4; ++d) ne[d] = t->ne[d];
+    if (i >= k->w.size()) return tts_kokoro_gen_weight(k->gen, i - k->w.size(), name, name_cap, ne, dst, cap);
+    const tts_tensor * t = k->w.tensor(i);
+    tg::weight_out(k->be, t, name, name_cap, ne, nullptr, nullptr, 0);
     return kokoro_read_weight(k->be, t, dst, cap);
 }
 
 extern "C" uint64_t tts_kokoro_get_node(tts_kokoro * k, int32_t which, const char * name, void * dst, uint64_t cap) {
-    if (!k || !name) return 0;
-    for (tts_tensor * t : (which ? k->gctx : k->dctx).nodes) {
-        if (strcmp(t->name, name) != 0 || !tg::is_contiguous(t)) continue;
-        const uint64_t nb = tg::nbytes(t);
-        if (dst && cap >= nb && k->be.get(k->be.ctx, dst, t->data, nb) != 0) return 0;
-        return nb;
-    }
-    return 0;
+    return k && name ? tg::named_node_out(k->be, (which ? k->gctx : k->dctx).nodes, name, dst, cap) : 0;
 }
 
 extern "C" tts_tensor * const * tts_kokoro_graph(const tts_kokoro * k, int32_t which, int32_t * n_nodes) {
-    const tg::context * c = k ? (which ? &k->gctx : &k->dctx) : nullptr;
-    if (n_nodes) *n_nodes = c ? (int32_t)c->nodes.size() : 0;
-    return c ? c->nodes.data() : nullptr;
+    return tg::graph_out(k ? (which ? &k->gctx : &k->dctx) : nullptr, n_nodes);
 }

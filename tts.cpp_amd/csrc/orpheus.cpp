@@ -16,7 +16,7 @@
 
 #include "../../include/tts_runners.h"
 #include "graph.h"
-#include "synth.h"
+#include "weights.h"
 
 using namespace tts;
 
@@ -27,9 +27,7 @@ struct orpheus_layer {
 struct tts_orpheus {
     tts_orpheus_config cfg;
     tts_backend_iface be;
-    tg::context wctx;
-    void * wbuf = nullptr;
-    size_t wbytes = 0;
+    weight_store w;  // the weights (declaration order), and the caches' tensors in its context
     void * kvbuf = nullptr;
     std::vector<orpheus_layer> layers;
     tts_tensor *embd = nullptr, *head = nullptr, *output_norm = nullptr, *rope_frequencies = nullptr;
@@ -46,13 +44,11 @@ struct tts_orpheus {
     void * launched_out = nullptr;
     int64_t host_steps = 0;
     std::vector<std::vector<int32_t>> output_tokens;
-    uint64_t tensor_index = 0;
     // seeded sampling (tts_orpheus_set_sampling); greedy when off
     bool sampling = false;
     tts_sampling samp{};
     int64_t sample_calls = 0;
     std::vector<int32_t> rep_last, rep_count;  // [batch]
-    std::vector<tts_tensor *> wlist;  // every weight, declaration order (tts_orpheus_weight)
 };
 
 extern "C" void tts_orpheus_set_sampling(tts_orpheus * p, const tts_sampling * cfg) {
@@ -82,15 +78,6 @@ extern "C" void tts_orpheus_default_config(tts_orpheus_config * c) {
     c->pad_ = 0;
 }
 
-static tts_tensor * wnew(tts_orpheus * p, std::vector<std::pair<tts_tensor *, int>> & specs, int type, int64_t ne0, int64_t ne1,
-                         int kind, const std::string & name) {
-    tts_tensor * t = ne1 > 1 ? tg::new_tensor_2d(p->wctx, type, ne0, ne1) : tg::new_tensor_1d(p->wctx, type, ne0);
-    tg::set_name(t, name);
-    t->flags |= tg::TG_FLAG_PERSIST;
-    specs.push_back({t, kind});
-    return t;
-}
-
 // orpheus_gguf_encoder.prepare_rope_frequencies (py-gguf/tts_encoders/orpheus_gguf_encoder.py:144-173)
 static void rope_factors(const tts_orpheus_config & cf, float * out) {
     const int dim = cf.head_size;
@@ -110,29 +97,15 @@ static void rope_factors(const tts_orpheus_config & cf, float * out) {
     }
 }
 
-static bool upload_weights(tts_orpheus * p, std::vector<std::pair<tts_tensor *, int>> & specs) {
-    size_t total = 0;
-    for (auto & s : specs) total += (tg::nbytes(s.first) + 255) & ~(size_t)255;
-    p->wbuf = p->be.alloc(p->be.ctx, total);
-    if (!p->wbuf) return false;
-    p->wbytes = total;
-    size_t off = 0;
-    std::vector<char> host;
-    uint64_t idx = 0;
-    for (auto & s : specs) {
-        tts_tensor * t = s.first;
-        const uint64_t seed = p->cfg.seed ^ (idx++);
-        const size_t nb = tg::nbytes(t);
-        t->data = (char *)p->wbuf + off;
-        off += (nb + 255) & ~(size_t)255;
-        host.resize(nb);
-        const int64_t K = t->ne[0], rows = tg::nelements(t) / t->ne[0];
-        if (s.second == 1) synth_f32((float *)host.data(), (size_t)(K * rows), seed, 0.1f, 1.0f);       // norm weights ~1
-        else if (s.second == 4) rope_factors(p->cfg, (float *)host.data());                             // rope factors
-        else synth_fill(t->type, host.data(), rows, K, seed, s.second == 3 ? 0.25f : 0.02f);          // matrices / embd
-        if (p->be.set_tensor(p->be.ctx, t, host.data()) != 0) return false;
+// kind: 0 = matrix, 1 = norm weight (~1), 3 = embedding, 4 = the computed rope factors
+static tts_tensor * wnew(tts_orpheus * p, int type, int64_t ne0, int64_t ne1, int kind, const std::string & name) {
+    weight_fill fill = kind == 1 ? weight_fill::uniform(0.1f, 1.0f) : weight_fill::matrix(kind == 3 ? 0.25f : 0.02f);
+    if (kind == 4) {
+        std::vector<float> f((size_t)ne0);
+        rope_factors(p->cfg, f.data());
+        fill = weight_fill::host(f.data(), f.size() * sizeof(float));
     }
-    return true;
+    return p->w.add(type, ne0, ne1, 1, name, fill, p->cfg.seed ^ p->w.index());
 }
 
 extern "C" tts_orpheus * tts_orpheus_create(const tts_backend_iface * be, const tts_orpheus_config * cfg) {
@@ -146,27 +119,25 @@ extern "C" tts_orpheus * tts_orpheus_create(const tts_backend_iface * be, const 
         delete p;
         return nullptr;
     }
-    std::vector<std::pair<tts_tensor *, int>> specs;
-    p->embd = wnew(p, specs, cf.weight_type, H, cf.vocab_size, 3, "token_embd");
-    p->head = wnew(p, specs, cf.weight_type, H, cf.vocab_size, 0, "output");
-    p->output_norm = wnew(p, specs, TTS_TYPE_F32, H, 1, 1, "output_norm");
-    p->rope_frequencies = wnew(p, specs, TTS_TYPE_F32, cf.head_size / 2, 1, 4, "rope_frequencies");
+    p->embd = wnew(p, cf.weight_type, H, cf.vocab_size, 3, "token_embd");
+    p->head = wnew(p, cf.weight_type, H, cf.vocab_size, 0, "output");
+    p->output_norm = wnew(p, TTS_TYPE_F32, H, 1, 1, "output_norm");
+    p->rope_frequencies = wnew(p, TTS_TYPE_F32, cf.head_size / 2, 1, 4, "rope_frequencies");
     p->layers.resize(cf.n_layers);
     for (int l = 0; l < cf.n_layers; ++l) {
         orpheus_layer & L = p->layers[l];
         const std::string pre = "layers." + std::to_string(l);
-        L.input_norm = wnew(p, specs, TTS_TYPE_F32, H, 1, 1, pre + ".input_norm");
-        L.q = wnew(p, specs, cf.weight_type, H, H, 0, pre + ".q");
-        L.k = wnew(p, specs, cf.weight_type, H, KVH, 0, pre + ".k");
-        L.v = wnew(p, specs, cf.weight_type, H, KVH, 0, pre + ".v");
-        L.o = wnew(p, specs, cf.weight_type, H, H, 0, pre + ".o");
-        L.post_attention_norm = wnew(p, specs, TTS_TYPE_F32, H, 1, 1, pre + ".post_attention_norm");
-        L.gate = wnew(p, specs, cf.weight_type, H, cf.ffn_size, 0, pre + ".gate");
-        L.up = wnew(p, specs, cf.weight_type, H, cf.ffn_size, 0, pre + ".up");
-        L.down = wnew(p, specs, cf.weight_type, cf.ffn_size, H, 0, pre + ".down");
+        L.input_norm = wnew(p, TTS_TYPE_F32, H, 1, 1, pre + ".input_norm");
+        L.q = wnew(p, cf.weight_type, H, H, 0, pre + ".q");
+        L.k = wnew(p, cf.weight_type, H, KVH, 0, pre + ".k");
+        L.v = wnew(p, cf.weight_type, H, KVH, 0, pre + ".v");
+        L.o = wnew(p, cf.weight_type, H, H, 0, pre + ".o");
+        L.post_attention_norm = wnew(p, TTS_TYPE_F32, H, 1, 1, pre + ".post_attention_norm");
+        L.gate = wnew(p, cf.weight_type, H, cf.ffn_size, 0, pre + ".gate");
+        L.up = wnew(p, cf.weight_type, H, cf.ffn_size, 0, pre + ".up");
+        L.down = wnew(p, cf.weight_type, cf.ffn_size, H, 0, pre + ".down");
     }
-    for (auto & s : specs) p->wlist.push_back(s.first);
-    if (!upload_weights(p, specs)) {
+    if (!p->w.upload(p->be)) {
         fprintf(stderr, "orpheus: weight allocation/upload failed\n");
         tts_orpheus_free(p);
         return nullptr;
@@ -181,10 +152,10 @@ extern "C" tts_orpheus * tts_orpheus_create(const tts_backend_iface * be, const 
     p->be.memset(p->be.ctx, p->kvbuf, 0, 2 * kvl * cf.n_layers);
     char * kp = (char *)p->kvbuf;
     for (int l = 0; l < cf.n_layers; ++l) {
-        tts_tensor * k = tg::new_tensor_1d(p->wctx, TTS_TYPE_F32, H * cf.max_ctx * cf.batch);
+        tts_tensor * k = tg::new_tensor_1d(p->w.wctx, TTS_TYPE_F32, H * cf.max_ctx * cf.batch);
         k->data = kp;
         kp += kvl;
-        tts_tensor * v = tg::new_tensor_1d(p->wctx, TTS_TYPE_F32, H * cf.max_ctx * cf.batch);
+        tts_tensor * v = tg::new_tensor_1d(p->w.wctx, TTS_TYPE_F32, H * cf.max_ctx * cf.batch);
         v->data = kp;
         kp += kvl;
         tg::set_name(k, "cache_k_l" + std::to_string(l));
@@ -206,7 +177,7 @@ extern "C" void tts_orpheus_free(tts_orpheus * p) {
     if (!p) return;
     if (p->arena) p->be.free(p->be.ctx, p->arena);
     if (p->kvbuf) p->be.free(p->be.ctx, p->kvbuf);
-    if (p->wbuf) p->be.free(p->be.ctx, p->wbuf);
+    p->w.release(p->be);
     delete p;
 }
 
@@ -481,14 +452,13 @@ extern "C" int tts_orpheus_generate(tts_orpheus * p, const int32_t * first_token
 
 extern "C" int32_t tts_orpheus_position(const tts_orpheus * p) { return p->position; }
 extern "C" int32_t tts_orpheus_last_graph_nodes(const tts_orpheus * p) { return p->last_nodes; }
-extern "C" uint64_t tts_orpheus_weight_bytes(const tts_orpheus * p) { return p->wbytes; }
-extern "C" int32_t tts_orpheus_n_weights(const tts_orpheus * p) { return p ? (int32_t)p->wlist.size() : 0; }
+extern "C" uint64_t tts_orpheus_weight_bytes(const tts_orpheus * p) { return p->w.wbytes; }
+extern "C" int32_t tts_orpheus_n_weights(const tts_orpheus * p) { return p ? p->w.size() : 0; }
 extern "C" uint64_t tts_orpheus_weight(tts_orpheus * p, int32_t i, char * name, uint64_t name_cap, int64_t * ne, int32_t * type, void * dst,
                                        uint64_t cap) {
-    if (!p || i < 0 || i >= (int32_t)p->wlist.size()) return 0;
-    return tg::weight_out(p->be, p->wlist[i], name, name_cap, ne, type, dst, cap);
+    const tts_tensor * t = p ? p->w.tensor(i) : nullptr;
+    return t ? tg::weight_out(p->be, t, name, name_cap, ne, type, dst, cap) : 0;
 }
 extern "C" tts_tensor * const * tts_orpheus_graph(const tts_orpheus * p, int32_t * n_nodes) {
-    if (n_nodes) *n_nodes = p ? (int32_t)p->gctx.nodes.size() : 0;
-    return p ? p->gctx.nodes.data() : nullptr;
+    return tg::graph_out(p ? &p->gctx : nullptr, n_nodes);
 }

@@ -21,7 +21,7 @@
 #include "../../include/tts_gguf.h"
 #include "../../include/tts_runners.h"
 #include "graph.h"
-#include "synth.h"
+#include "weights.h"
 
 using namespace tts;
 
@@ -35,9 +35,7 @@ struct parler_layer {
 struct tts_parler {
     tts_parler_config cfg;
     tts_backend_iface be;
-    tg::context wctx;
-    void * wbuf = nullptr;
-    size_t wbytes = 0;
+    weight_store w;  // the weights (declaration order), and the caches' tensors in its context
     void * kvbuf = nullptr;
     size_t kvbytes = 0;
     std::vector<tts_tensor *> embds, heads;
@@ -68,14 +66,11 @@ struct tts_parler {
     int64_t host_steps = 0;
     std::vector<std::vector<int32_t>> output_tokens;  // per sequence, flat [steps][heads]
     std::vector<std::vector<char>> eos_seen;
-    uint64_t tensor_index = 0;
     // seeded sampling (tts_parler_set_sampling); greedy (sampler::max) when off
     bool sampling = false;
     tts_sampling samp{};
     int64_t sample_calls = 0;                 // sampler::sample calls so far (one per step)
     std::vector<int32_t> rep_last, rep_count;  // [batch][heads] repetition-penalty state
-    const tts_gguf * gguf = nullptr;  // weight source while creating from a file (else synthetic)
-    std::vector<tts_tensor *> wlist;  // every weight, declaration order (tts_parler_weight)
 };
 
 extern "C" void tts_parler_default_config(tts_parler_config * c) {
@@ -103,101 +98,16 @@ extern "C" void tts_parler_default_config(tts_parler_config * c) {
 }
 
 // ---- weights ----
-struct wspec {
-    tts_tensor * t;
-    int kind;  // 0 = matrix (synth_fill), 1 = norm weight (~1), 2 = bias (~0), 3 = embedding f32
-    uint64_t seed;
-};
-
-// Tensor names are the GGUF names without the "decoder." prefix (parler/model.cpp:4-27, :501-505).
-static std::string gguf_name(const tts_tensor * t) { return std::string("decoder.") + t->name; }
-
-static tts_tensor * wnew(tts_parler * p, std::vector<wspec> & specs, int type, int64_t ne0, int64_t ne1, int kind,
-                         const std::string & name) {
-    if (p->gguf) {  // the file decides the storage type (quantize_impl.cpp's per-tensor rules)
-        const int64_t i = tts_gguf_find_tensor(p->gguf, ("decoder." + name).c_str());
-        if (i >= 0) type = tts_gguf_tensor_type(p->gguf, i);
-    }
-    tts_tensor * t = ne1 > 1 ? tg::new_tensor_2d(p->wctx, type, ne0, ne1) : tg::new_tensor_1d(p->wctx, type, ne0);
-    tg::set_name(t, name);
-    t->flags |= tg::TG_FLAG_PERSIST;
-    specs.push_back({t, kind, p->cfg.seed ^ (p->tensor_index++)});
-    return t;
-}
-
-// The synthetic bytes tts_parler_create uploads for a spec (host).
-static void synth_host(const wspec & s, std::vector<char> & host) {
-    const tts_tensor * t = s.t;
-    host.resize(tg::nbytes(t));
-    const int64_t K = t->ne[0], rows = tg::nelements(t) / t->ne[0];
-    const int kind = (t->type == TTS_TYPE_F32) ? s.kind : 0;
-    const float std = s.kind == 3 ? 0.25f : 0.02f;
-    switch (kind) {
-        case 1: synth_f32((float *)host.data(), (size_t)(K * rows), s.seed, 0.1f, 1.0f); break;
-        case 2: synth_f32((float *)host.data(), (size_t)(K * rows), s.seed, 0.02f, 0.0f); break;
-        case 3: synth_f32((float *)host.data(), (size_t)(K * rows), s.seed, 0.5f, 0.0f); break;
-        default: synth_fill(t->type, host.data(), rows, K, s.seed, std); break;
-    }
-}
-
-// Same elements in the same order: equal after dropping the 1-sized dimensions (a GGUF bias [C]
-// against a [1, C] tensor, assign_to_layer's transposed dup).
-static bool same_squeezed_shape(const int64_t * a, const int64_t * b) {
-    int64_t x[4], y[4];
-    int nx = 0, ny = 0;
-    for (int d = 0; d < 4; ++d) {
-        if (a[d] != 1) x[nx++] = a[d];
-        if (b[d] != 1) y[ny++] = b[d];
-    }
-    if (nx != ny) return false;
-    for (int d = 0; d < nx; ++d)
-        if (x[d] != y[d]) return false;
-    return true;
-}
-
-// File tensor for t: present, same type and element layout; NULL (reason on stderr) otherwise.
-static const void * gguf_source(const tts_gguf * g, const std::string & fname, const tts_tensor * t) {
-    const int64_t i = tts_gguf_find_tensor(g, fname.c_str());
-    if (i < 0) {
-        fprintf(stderr, "gguf: tensor '%s' is missing\n", fname.c_str());
-        return nullptr;
-    }
-    int64_t ne[4];
-    tts_gguf_tensor_ndims(g, i, ne);
-    if (tts_gguf_tensor_type(g, i) != t->type || !same_squeezed_shape(ne, t->ne) || tts_gguf_tensor_size(g, i) != tg::nbytes(t)) {
-        fprintf(stderr, "gguf: tensor '%s' has type %d [%lld %lld %lld %lld], the runner needs type %d [%lld %lld %lld %lld]\n", fname.c_str(),
-                tts_gguf_tensor_type(g, i), (long long)ne[0], (long long)ne[1], (long long)ne[2], (long long)ne[3], t->type, (long long)t->ne[0],
-                (long long)t->ne[1], (long long)t->ne[2], (long long)t->ne[3]);
-        return nullptr;
-    }
-    return tts_gguf_tensor_data(g, i);
-}
-
-static bool upload_weights(tts_parler * p, std::vector<wspec> & specs) {
-    size_t total = 0;
-    for (auto & s : specs) total += (tg::nbytes(s.t) + 255) & ~(size_t)255;
-    p->wbuf = p->be.alloc(p->be.ctx, total);
-    if (!p->wbuf) return false;
-    p->wbytes = total;
-    size_t off = 0;
-    std::vector<char> host;
-    for (auto & s : specs) {
-        tts_tensor * t = s.t;
-        const size_t nb = tg::nbytes(t);
-        t->data = (char *)p->wbuf + off;
-        off += (nb + 255) & ~(size_t)255;
-        const void * src;
-        if (p->gguf) {  // assign_weight: the mapped file bytes, uploaded whole
-            src = gguf_source(p->gguf, gguf_name(t), t);
-            if (!src) return false;
-        } else {
-            synth_host(s, host);
-            src = host.data();
-        }
-        // whole-tensor upload: the backend may keep its own layout (HIP: Q4_K lane layout)
-        if (p->be.set_tensor(p->be.ctx, t, src) != 0) return false;
-    }
-    return true;
+// kind: 0 = matrix, 1 = norm weight (~1), 2 = bias (~0), 3 = embedding; 1..3 only as F32, any other
+// storage type is a matrix.  With a file attached it decides the storage type (quantize_impl.cpp's
+// per-tensor rules).
+static tts_tensor * wnew(tts_parler * p, int type, int64_t ne0, int64_t ne1, int kind, const std::string & name) {
+    type = p->w.file_type(name, type);
+    const weight_fill fill = type != TTS_TYPE_F32 || kind == 0 ? weight_fill::matrix(kind == 3 ? 0.25f : 0.02f)
+                             : kind == 1                       ? weight_fill::uniform(0.1f, 1.0f)
+                             : kind == 2                       ? weight_fill::uniform(0.02f, 0.0f)
+                                                               : weight_fill::uniform(0.5f, 0.0f);
+    return p->w.add(type, ne0, ne1, 1, name, fill, p->cfg.seed ^ p->w.index());
 }
 
 static tts_tensor * layer_norm(tg::context & c, tts_tensor * x, tts_tensor * w, tts_tensor * b) {
@@ -246,40 +156,41 @@ static bool prep_cross_key_values(tts_parler * p) {
 extern "C" void tts_parler_free(tts_parler * p);
 
 // Declares every weight tensor in the reference's order (synthetic seeds follow this order).
-static void declare_weights(tts_parler * p, std::vector<wspec> & specs) {
+static void declare_weights(tts_parler * p) {
     const auto & cf = p->cfg;
+    p->w.prefix = "decoder.";  // parler/model.cpp:4-27, :501-505
     const int64_t H = cf.hidden_size;
     // decoder.embed_tokens.{i} (Q4_K when quantized), decoder.lm_heads.{i}.weight.head (F32)
     for (int i = 0; i < cf.n_output_heads; ++i)
-        p->embds.push_back(wnew(p, specs, cf.weight_type, H, cf.output_vocab, 3, "embed_tokens." + std::to_string(i) + ".weight"));
+        p->embds.push_back(wnew(p, cf.weight_type, H, cf.output_vocab, 3, "embed_tokens." + std::to_string(i) + ".weight"));
     for (int i = 0; i < cf.n_output_heads; ++i)
-        p->heads.push_back(wnew(p, specs, cf.head_type, H, cf.output_vocab, 0, "lm_heads." + std::to_string(i) + ".weight.head"));
-    p->pos_embd = wnew(p, specs, TTS_TYPE_F32, H, cf.max_positions, 3, "positional_embed");
-    p->prompt_embd = wnew(p, specs, TTS_TYPE_F32, H, cf.prompt_vocab, 3, "embed_prompts");
-    p->text_encoding = wnew(p, specs, TTS_TYPE_F32, H, cf.n_encode, 3, "text_encoding");
-    p->norm = wnew(p, specs, TTS_TYPE_F32, H, 1, 1, "layer_norm.weight");
-    p->norm_b = wnew(p, specs, TTS_TYPE_F32, H, 1, 2, "layer_norm.bias");
+        p->heads.push_back(wnew(p, cf.head_type, H, cf.output_vocab, 0, "lm_heads." + std::to_string(i) + ".weight.head"));
+    p->pos_embd = wnew(p, TTS_TYPE_F32, H, cf.max_positions, 3, "positional_embed");
+    p->prompt_embd = wnew(p, TTS_TYPE_F32, H, cf.prompt_vocab, 3, "embed_prompts");
+    p->text_encoding = wnew(p, TTS_TYPE_F32, H, cf.n_encode, 3, "text_encoding");
+    p->norm = wnew(p, TTS_TYPE_F32, H, 1, 1, "layer_norm.weight");
+    p->norm_b = wnew(p, TTS_TYPE_F32, H, 1, 2, "layer_norm.bias");
     p->layers.resize(cf.n_layers);
     for (int l = 0; l < cf.n_layers; ++l) {
         parler_layer & L = p->layers[l];
         const std::string pre = "layers." + std::to_string(l);
-        L.q = wnew(p, specs, cf.weight_type, H, H, 0, pre + ".self_attn.q_proj.weight");
-        L.k = wnew(p, specs, cf.weight_type, H, H, 0, pre + ".self_attn.k_proj.weight");
-        L.v = wnew(p, specs, cf.weight_type, H, H, 0, pre + ".self_attn.v_proj.weight");
-        L.o = wnew(p, specs, cf.weight_type, H, H, 0, pre + ".self_attn.out_proj.weight");
-        L.sa_norm = wnew(p, specs, TTS_TYPE_F32, H, 1, 1, pre + ".self_attn_layer_norm.weight");
-        L.sa_norm_b = wnew(p, specs, TTS_TYPE_F32, H, 1, 2, pre + ".self_attn_layer_norm.bias");
-        L.aq = wnew(p, specs, cf.weight_type, H, H, 0, pre + ".encoder_attn.q_proj.weight");
+        L.q = wnew(p, cf.weight_type, H, H, 0, pre + ".self_attn.q_proj.weight");
+        L.k = wnew(p, cf.weight_type, H, H, 0, pre + ".self_attn.k_proj.weight");
+        L.v = wnew(p, cf.weight_type, H, H, 0, pre + ".self_attn.v_proj.weight");
+        L.o = wnew(p, cf.weight_type, H, H, 0, pre + ".self_attn.out_proj.weight");
+        L.sa_norm = wnew(p, TTS_TYPE_F32, H, 1, 1, pre + ".self_attn_layer_norm.weight");
+        L.sa_norm_b = wnew(p, TTS_TYPE_F32, H, 1, 2, pre + ".self_attn_layer_norm.bias");
+        L.aq = wnew(p, cf.weight_type, H, H, 0, pre + ".encoder_attn.q_proj.weight");
         // encoder_attn k/v stay F32 (quantize_impl.cpp: quantize_cross_attn_kv off by default)
-        L.ak = wnew(p, specs, TTS_TYPE_F32, H, H, 0, pre + ".encoder_attn.k_proj.weight");
-        L.av = wnew(p, specs, TTS_TYPE_F32, H, H, 0, pre + ".encoder_attn.v_proj.weight");
-        L.ao = wnew(p, specs, cf.weight_type, H, H, 0, pre + ".encoder_attn.out_proj.weight");
-        L.a_norm = wnew(p, specs, TTS_TYPE_F32, H, 1, 1, pre + ".encoder_attn_layer_norm.weight");
-        L.a_norm_b = wnew(p, specs, TTS_TYPE_F32, H, 1, 2, pre + ".encoder_attn_layer_norm.bias");
-        L.fc1 = wnew(p, specs, cf.weight_type, H, cf.ffn_size, 0, pre + ".fc1.weight");
-        L.fc2 = wnew(p, specs, cf.weight_type, cf.ffn_size, H, 0, pre + ".fc2.weight");
-        L.f_norm = wnew(p, specs, TTS_TYPE_F32, H, 1, 1, pre + ".final_layer_norm.weight");
-        L.f_norm_b = wnew(p, specs, TTS_TYPE_F32, H, 1, 2, pre + ".final_layer_norm.bias");
+        L.ak = wnew(p, TTS_TYPE_F32, H, H, 0, pre + ".encoder_attn.k_proj.weight");
+        L.av = wnew(p, TTS_TYPE_F32, H, H, 0, pre + ".encoder_attn.v_proj.weight");
+        L.ao = wnew(p, cf.weight_type, H, H, 0, pre + ".encoder_attn.out_proj.weight");
+        L.a_norm = wnew(p, TTS_TYPE_F32, H, 1, 1, pre + ".encoder_attn_layer_norm.weight");
+        L.a_norm_b = wnew(p, TTS_TYPE_F32, H, 1, 2, pre + ".encoder_attn_layer_norm.bias");
+        L.fc1 = wnew(p, cf.weight_type, H, cf.ffn_size, 0, pre + ".fc1.weight");
+        L.fc2 = wnew(p, cf.weight_type, cf.ffn_size, H, 0, pre + ".fc2.weight");
+        L.f_norm = wnew(p, TTS_TYPE_F32, H, 1, 1, pre + ".final_layer_norm.weight");
+        L.f_norm_b = wnew(p, TTS_TYPE_F32, H, 1, 2, pre + ".final_layer_norm.bias");
     }
 }
 
@@ -287,16 +198,14 @@ static tts_parler * parler_create(const tts_backend_iface * be, const tts_parler
     auto * p = new tts_parler();
     p->cfg = *cfg;
     p->be = *be;
-    p->gguf = g;
+    p->w.attach(g);
     const auto & cf = p->cfg;
     const int64_t H = cf.hidden_size;
     const int hd = cf.hidden_size / cf.n_attn_heads;
     const int B = cf.batch < 1 ? 1 : cf.batch;
     p->cfg.batch = B;
-    std::vector<wspec> specs;
-    declare_weights(p, specs);
-    for (auto & s : specs) p->wlist.push_back(s.t);
-    if (!upload_weights(p, specs)) {
+    declare_weights(p);
+    if (!p->w.upload(p->be)) {
         fprintf(stderr, "parler: weight allocation/upload failed\n");
         tts_parler_free(p);
         return nullptr;
@@ -315,18 +224,18 @@ static tts_parler * parler_create(const tts_backend_iface * be, const tts_parler
     char * kp = (char *)p->kvbuf;
     for (int l = 0; l < cf.n_layers; ++l) {
         parler_layer & L = p->layers[l];
-        L.cross_k = tg::new_tensor_3d(p->wctx, TTS_TYPE_F32, hd, cf.n_encode, cf.n_attn_heads);
+        L.cross_k = tg::new_tensor_3d(p->w.wctx, TTS_TYPE_F32, hd, cf.n_encode, cf.n_attn_heads);
         L.cross_k->data = kp;
         kp += (ck + 255) & ~(size_t)255;
-        if (B > 1) L.cross_v = tg::new_tensor_4d(p->wctx, TTS_TYPE_F32, cf.n_encode, hd, cf.n_attn_heads, B);
-        else L.cross_v = tg::new_tensor_3d(p->wctx, TTS_TYPE_F32, cf.n_encode, hd, cf.n_attn_heads);
+        if (B > 1) L.cross_v = tg::new_tensor_4d(p->w.wctx, TTS_TYPE_F32, cf.n_encode, hd, cf.n_attn_heads, B);
+        else L.cross_v = tg::new_tensor_3d(p->w.wctx, TTS_TYPE_F32, cf.n_encode, hd, cf.n_attn_heads);
         L.cross_v->data = kp;
         kp += (cv + 255) & ~(size_t)255;
         // parler_kv_cache_init: 1-D F32 [hidden*max_ctx] per layer (x B sequences)
-        tts_tensor * k = tg::new_tensor_1d(p->wctx, TTS_TYPE_F32, H * cf.max_ctx * B);
+        tts_tensor * k = tg::new_tensor_1d(p->w.wctx, TTS_TYPE_F32, H * cf.max_ctx * B);
         k->data = kp;
         kp += kvl;
-        tts_tensor * v = tg::new_tensor_1d(p->wctx, TTS_TYPE_F32, H * cf.max_ctx * B);
+        tts_tensor * v = tg::new_tensor_1d(p->w.wctx, TTS_TYPE_F32, H * cf.max_ctx * B);
         v->data = kp;
         kp += kvl;
         tg::set_name(k, "cache_k_l" + std::to_string(l));
@@ -345,7 +254,6 @@ static tts_parler * parler_create(const tts_backend_iface * be, const tts_parler
         tts_parler_free(p);
         return nullptr;
     }
-    p->gguf = nullptr;
     tts_parler_reset(p);
     return p;
 }
@@ -356,7 +264,7 @@ extern "C" void tts_parler_free(tts_parler * p) {
     if (!p) return;
     if (p->arena) p->be.free(p->be.ctx, p->arena);
     if (p->kvbuf) p->be.free(p->be.ctx, p->kvbuf);
-    if (p->wbuf) p->be.free(p->be.ctx, p->wbuf);
+    p->w.release(p->be);
     delete p;
 }
 
@@ -866,70 +774,34 @@ extern "C" int64_t tts_parler_host_stats(tts_parler * p, double * us5, int reset
     return n;
 }
 extern "C" int32_t tts_parler_last_graph_nodes(const tts_parler * p) { return p->last_nodes; }
-extern "C" int32_t tts_parler_n_weights(const tts_parler * p) { return p ? (int32_t)p->wlist.size() : 0; }
+extern "C" int32_t tts_parler_n_weights(const tts_parler * p) { return p ? p->w.size() : 0; }
 extern "C" uint64_t tts_parler_weight(tts_parler * p, int32_t i, char * name, uint64_t name_cap, int64_t * ne, int32_t * type, void * dst,
                                       uint64_t cap) {
-    if (!p || i < 0 || i >= (int32_t)p->wlist.size()) return 0;
-    return tg::weight_out(p->be, p->wlist[i], name, name_cap, ne, type, dst, cap);
+    const tts_tensor * t = p ? p->w.tensor(i) : nullptr;
+    return t ? tg::weight_out(p->be, t, name, name_cap, ne, type, dst, cap) : 0;
 }
-extern "C" uint64_t tts_parler_weight_bytes(const tts_parler * p) { return p->wbytes; }
+extern "C" uint64_t tts_parler_weight_bytes(const tts_parler * p) { return p->w.wbytes; }
 
 // The last step graph's node list (valid until the next step is prepared), e.g. for tts_hip_plan_stats.
 extern "C" tts_tensor * const * tts_parler_graph(const tts_parler * p, int32_t * n_nodes) {
-    if (n_nodes) *n_nodes = p ? (int32_t)p->gctx.nodes.size() : 0;
-    return p ? p->gctx.nodes.data() : nullptr;
+    return tg::graph_out(p ? &p->gctx : nullptr, n_nodes);
 }
 
 // Debug: node i of the last step graph -> op, type, ne[4]; copies its bytes if contiguous and cap fits.
 extern "C" uint64_t tts_parler_node(tts_parler * p, int32_t i, int32_t * op, int32_t * type, int64_t * ne, void * dst, uint64_t cap) {
-    if (i < 0 || i >= (int32_t)p->gctx.nodes.size()) return 0;
-    const tts_tensor * t = p->gctx.nodes[i];
-    *op = t->op;
-    *type = t->type;
-    for (int k = 0; k < 4; ++k) ne[k] = t->ne[k];
-    if (!tg::is_contiguous(t) || !dst) return 0;
-    const size_t nb = tg::nbytes(t);
-    if (nb > cap) return 0;
-    if (p->be.get(p->be.ctx, dst, t->data, nb) != 0) return 0;
-    return nb;
+    return tg::node_out(p->be, p->gctx.nodes, i, op, type, ne, dst, cap);
 }
 
+// The first node called `name`, whole or not at all: 0 when it is not contiguous or cap is too small.
 extern "C" uint64_t tts_parler_get_node(tts_parler * p, const char * name, void * dst, uint64_t cap) {
-    for (auto * t : p->gctx.nodes) {
-        if (strcmp(t->name, name) == 0) {
-            if (!tg::is_contiguous(t)) return 0;
-            size_t nb = tg::nbytes(t);
-            if (nb > cap) return 0;
-            if (p->be.get(p->be.ctx, dst, t->data, nb) != 0) return 0;
-            return nb;
-        }
-    }
+    for (const tts_tensor * t : p->gctx.nodes)
+        if (strcmp(t->name, name) == 0) return dst && tg::nbytes(t) <= cap ? tg::tensor_out(p->be, t, dst, cap) : 0;
     return 0;
 }
 
 // ---- GGUF loader path (runner_from_file + parler_tts_model::prep_constants / assign_weight) ----
 namespace tts {
 void dac_write_synthetic(const tts_dac_config * cfg, tts_gguf_writer * w);
-}
-
-static bool gguf_u32(const tts_gguf * g, std::initializer_list<const char *> keys, int32_t * out) {
-    for (const char * k : keys) {  // search_for_gguf_keys: first key present wins
-        const int64_t i = tts_gguf_find_key(g, k);
-        uint32_t v;
-        if (i >= 0 && tts_gguf_get_u32(g, i, &v)) {
-            *out = (int32_t)v;
-            return true;
-        }
-    }
-    return false;
-}
-
-static int64_t gguf_dim(const tts_gguf * g, const char * name, int d) {
-    const int64_t i = tts_gguf_find_tensor(g, name);
-    if (i < 0) return -1;
-    int64_t ne[4];
-    tts_gguf_tensor_ndims(g, i, ne);
-    return ne[d];
 }
 
 extern "C" int tts_parler_config_from_gguf(const tts_gguf * g, tts_parler_config * c) {
@@ -940,22 +812,22 @@ extern "C" int tts_parler_config_from_gguf(const tts_gguf * g, tts_parler_config
         return TTS_STATUS_BAD_ARG;
     }
     // prep_constants (model.cpp:51-108); encode_length is the one required key
-    if (!gguf_u32(g, {"parler-tts.decoder.encode_length", "encode_length"}, &c->n_encode)) {
+    if (!gguf_first_u32(g, {"parler-tts.decoder.encode_length", "encode_length"}, &c->n_encode)) {
         fprintf(stderr, "gguf: key 'parler-tts.decoder.encode_length' must be specified\n");
         return TTS_STATUS_BAD_ARG;
     }
-    gguf_u32(g, {"parler-tts.decoder.hidden_size", "hidden_size"}, &c->hidden_size);
-    gguf_u32(g, {"parler-tts.decoder.output_heads", "output_heads"}, &c->n_output_heads);
-    gguf_u32(g, {"parler-tts.decoder.attention.head_count", "attn_heads"}, &c->n_attn_heads);
-    gguf_u32(g, {"parler-tts.decoder.out_vocab_size", "out_vocab_size"}, &c->output_vocab);
-    gguf_u32(g, {"parler-tts.decoder.audio_vocab_size", "audio_vocab_size"}, &c->audio_vocab);
-    gguf_u32(g, {"parler-tts.decoder.num_hidden_layers", "num_hidden_layers"}, &c->n_layers);
-    gguf_u32(g, {"audio.bos_token_id", "bos_token_id"}, &c->bos_token);
-    gguf_u32(g, {"audio.eos_token_id", "eos_token_id"}, &c->eos_token);
+    gguf_first_u32(g, {"parler-tts.decoder.hidden_size", "hidden_size"}, &c->hidden_size);
+    gguf_first_u32(g, {"parler-tts.decoder.output_heads", "output_heads"}, &c->n_output_heads);
+    gguf_first_u32(g, {"parler-tts.decoder.attention.head_count", "attn_heads"}, &c->n_attn_heads);
+    gguf_first_u32(g, {"parler-tts.decoder.out_vocab_size", "out_vocab_size"}, &c->output_vocab);
+    gguf_first_u32(g, {"parler-tts.decoder.audio_vocab_size", "audio_vocab_size"}, &c->audio_vocab);
+    gguf_first_u32(g, {"parler-tts.decoder.num_hidden_layers", "num_hidden_layers"}, &c->n_layers);
+    gguf_first_u32(g, {"audio.bos_token_id", "bos_token_id"}, &c->bos_token);
+    gguf_first_u32(g, {"audio.eos_token_id", "eos_token_id"}, &c->eos_token);
     // sizes the reference takes from the tensors themselves
-    const int64_t ffn = gguf_dim(g, "decoder.layers.0.fc1.weight", 1);
-    const int64_t pv = gguf_dim(g, "decoder.embed_prompts", 1);
-    const int64_t mp = gguf_dim(g, "decoder.positional_embed", 1);
+    const int64_t ffn = gguf_tensor_dim(g, "decoder.layers.0.fc1.weight", 1);
+    const int64_t pv = gguf_tensor_dim(g, "decoder.embed_prompts", 1);
+    const int64_t mp = gguf_tensor_dim(g, "decoder.positional_embed", 1);
     const int64_t wt = tts_gguf_find_tensor(g, "decoder.layers.0.self_attn.q_proj.weight");
     const int64_t ht = tts_gguf_find_tensor(g, "decoder.lm_heads.0.weight.head");
     if (ffn < 0 || pv < 0 || mp < 0 || wt < 0 || ht < 0) {
@@ -984,8 +856,7 @@ extern "C" int tts_parler_write_synthetic_gguf(const tts_parler_config * cfg, co
     if (!cfg || !path) return TTS_STATUS_BAD_ARG;
     tts_parler p;  // declarations only: no backend, no buffers
     p.cfg = *cfg;
-    std::vector<wspec> specs;
-    declare_weights(&p, specs);
+    declare_weights(&p);
     tts_gguf_writer * w = tts_gguf_writer_new();
     const auto & c = *cfg;
     // the keys prep_constants reads (parler_tts_gguf_encoder.py writes them)
@@ -1001,14 +872,7 @@ extern "C" int tts_parler_write_synthetic_gguf(const tts_parler_config * cfg, co
     tts_gguf_set_u32(w, "parler-tts.decoder.num_hidden_layers", (uint32_t)c.n_layers);
     tts_gguf_set_u32(w, "audio.bos_token_id", (uint32_t)c.bos_token);
     tts_gguf_set_u32(w, "audio.eos_token_id", (uint32_t)c.eos_token);
-    int st = TTS_STATUS_SUCCESS;
-    std::vector<char> host;
-    for (auto & s : specs) {
-        synth_host(s, host);
-        const int nd = s.t->ne[1] > 1 ? 2 : 1;
-        st = tts_gguf_add_tensor(w, gguf_name(s.t).c_str(), s.t->type, nd, s.t->ne, host.data(), host.size());
-        if (st != TTS_STATUS_SUCCESS) break;
-    }
+    int st = p.w.write(w);
     if (st == TTS_STATUS_SUCCESS && dac_cfg) dac_write_synthetic(dac_cfg, w);
     if (st == TTS_STATUS_SUCCESS) st = tts_gguf_writer_write(w, path);
     tts_gguf_writer_free(w);

@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "graph.h"
-#include "synth.h"
+#include "weights.h"
 #include "tts_hip.h"
 #include "tts_runners.h"
 
@@ -38,19 +38,12 @@ struct snac_quant {  // residual_vector_quantize_layer
     tts_tensor *codebook, *out_kernel, *out_bias;
 };
 
-struct wspec {
-    tts_tensor * t;
-    float scale, offset;
-    uint64_t seed;
-};
-
 }  // namespace
 
 struct tts_snac {
     tts_snac_config cfg;
     tts_backend_iface be;
-    tg::context wctx;
-    void * wbuf = nullptr;
+    weight_store w;  // the weights, declaration order
     std::vector<snac_quant> quant;
     tts_tensor *in_kernel = nullptr, *in_bias = nullptr, *up_kernel = nullptr, *up_bias = nullptr;
     tts_tensor *out_alpha = nullptr, *out_kernel = nullptr, *out_bias = nullptr;
@@ -60,8 +53,6 @@ struct tts_snac {
     size_t arena_size = 0;
     tg::context gctx;
     tts_tensor *in_codes = nullptr, *in_noise = nullptr;
-    uint64_t tensor_index = 0;
-    std::vector<wspec> specs;
 };
 
 extern "C" void tts_snac_default_config(tts_snac_config * c) {
@@ -82,34 +73,12 @@ extern "C" void tts_snac_default_config(tts_snac_config * c) {
 }
 
 static tts_tensor * wnew(tts_snac * d, float scale, float offset, int64_t ne0, int64_t ne1, int64_t ne2, const std::string & name) {
-    tts_tensor * t = tg::new_tensor_3d(d->wctx, TTS_TYPE_F32, ne0, ne1, ne2);
-    tg::set_name(t, name);
-    t->flags |= tg::TG_FLAG_PERSIST;
-    d->specs.push_back({t, scale, offset, d->cfg.seed ^ (d->tensor_index++)});
-    return t;
+    return d->w.add(TTS_TYPE_F32, ne0, ne1, ne2, name, weight_fill::uniform(scale, offset), d->cfg.seed ^ d->w.index());
 }
 
 // conv kernel [K, IC, OC], uniform +-gain*sqrt(3/fan_in)
 static tts_tensor * conv_w(tts_snac * d, int K, int IC, int OC, const std::string & name, float gain = 1.0f) {
     return wnew(d, gain * std::sqrt(3.0f / (float)(K * IC)), 0.f, K, IC, OC, name);
-}
-
-static bool upload(tts_snac * d) {
-    size_t total = 0;
-    for (auto & s : d->specs) total += (tg::nbytes(s.t) + 255) & ~(size_t)255;
-    d->wbuf = d->be.alloc(d->be.ctx, total);
-    if (!d->wbuf) return false;
-    size_t off = 0;
-    std::vector<float> host;
-    for (auto & s : d->specs) {
-        const size_t n = (size_t)tg::nelements(s.t);
-        s.t->data = (char *)d->wbuf + off;
-        off += (tg::nbytes(s.t) + 255) & ~(size_t)255;
-        host.resize(n);
-        synth_f32(host.data(), n, s.seed, s.scale, s.offset);
-        if (d->be.set_tensor(d->be.ctx, s.t, host.data()) != 0) return false;
-    }
-    return true;
 }
 
 static int64_t snac_hop(const tts_snac_config & c) {
@@ -167,7 +136,7 @@ extern "C" tts_snac * tts_snac_create(const tts_backend_iface * be, const tts_sn
     d->out_kernel = conv_w(d, 7, ch, 1, "final.weight", 0.1f);
     d->out_bias = wnew(d, 0.01f, 0.f, 1, 1, 1, "final.bias");
     d->one = wnew(d, 0.f, 1.0f, 1, 1, 1, "one");
-    if (!upload(d)) {
+    if (!d->w.upload(d->be)) {
         tts_snac_free(d);
         return nullptr;
     }
@@ -186,7 +155,7 @@ extern "C" tts_snac * tts_snac_create(const tts_backend_iface * be, const tts_sn
 extern "C" void tts_snac_free(tts_snac * d) {
     if (!d) return;
     if (d->arena) d->be.free(d->be.ctx, d->arena);
-    if (d->wbuf) d->be.free(d->be.ctx, d->wbuf);
+    d->w.release(d->be);
     delete d;
 }
 
@@ -303,30 +272,14 @@ extern "C" int tts_snac_decode(tts_snac * d, const int32_t * codes, int32_t T, c
 
 extern "C" int32_t tts_snac_last_graph_nodes(const tts_snac * d) { return (int32_t)d->gctx.nodes.size(); }
 
-extern "C" int32_t tts_snac_n_weights(const tts_snac * d) { return d ? (int32_t)d->specs.size() : 0; }
+extern "C" int32_t tts_snac_n_weights(const tts_snac * d) { return d ? d->w.size() : 0; }
 
 extern "C" uint64_t tts_snac_weight(tts_snac * d, int32_t i, char * name, uint64_t name_cap, int64_t * ne, float * dst, uint64_t cap) {
-    if (!d || i < 0 || i >= (int32_t)d->specs.size()) return 0;
-    const tts_tensor * t = d->specs[i].t;
-    if (name && name_cap) {
-        strncpy(name, t->name, name_cap - 1);
-        name[name_cap - 1] = 0;
-    }
-    if (ne)
-        for (int k = 0; k < 4; ++k) ne[k] = t->ne[k];
-    const uint64_t n = tg::nbytes(t);
-    if (dst && cap >= n && d->be.get(d->be.ctx, dst, t->data, n) != 0) return 0;
-    return n;
+    const tts_tensor * t = d ? d->w.tensor(i) : nullptr;
+    return t ? tg::weight_out(d->be, t, name, name_cap, ne, nullptr, dst, cap) : 0;
 }
 
 // Debug: copy the named node of the last graph to host (contiguous nodes only); returns bytes.
 extern "C" uint64_t tts_snac_get_node(tts_snac * d, const char * name, void * dst, uint64_t cap) {
-    if (!d || !name) return 0;
-    for (tts_tensor * t : d->gctx.nodes) {
-        if (strcmp(t->name, name) != 0 || !tg::is_contiguous(t)) continue;
-        const uint64_t n = tg::nbytes(t);
-        if (dst && cap >= n && d->be.get(d->be.ctx, dst, t->data, n) != 0) return 0;
-        return n;
-    }
-    return 0;
+    return d && name ? tg::named_node_out(d->be, d->gctx.nodes, name, dst, cap) : 0;
 }

@@ -15,7 +15,7 @@
 #include "../../include/tts_gguf.h"
 #include "../../include/tts_runners.h"
 #include "graph.h"
-#include "synth.h"
+#include "weights.h"
 
 using namespace tts;
 
@@ -23,29 +23,18 @@ struct t5_layer {
     tts_tensor *attn_norm, *q, *k, *v, *o, *mlp_norm, *wi_0, *wi_1, *wo;
 };
 
-struct t5_wspec {
-    tts_tensor * t;
-    int kind;  // 0 = matrix, 1 = norm weight (~1), 2 = bias (~0), 3 = embedding, 4 = relative attention bias
-    uint64_t seed;
-};
-
 struct tts_t5 {
     tts_t5_config cfg;
     tts_backend_iface be;
-    tg::context wctx;
-    void * wbuf = nullptr;
-    size_t wbytes = 0;
+    weight_store w;  // the weights, declaration order
     tts_tensor *embd = nullptr, *rel_bias = nullptr, *out_norm = nullptr, *down_proj = nullptr, *down_proj_bias = nullptr;
     std::vector<t5_layer> layers;
-    std::vector<tts_tensor *> wlist;  // every weight, declaration order (tts_t5_weight)
     char * arena = nullptr;
     size_t arena_size = 0;
     tg::context gctx;
     tts_tensor * res = nullptr;
     tts_tensor *in_tokens = nullptr, *in_pos_bucket = nullptr, *in_mask = nullptr;
     int32_t last_nodes = 0;
-    uint64_t tensor_index = 0;
-    const tts_gguf * gguf = nullptr;  // weight source while creating from a file (else synthetic)
 };
 
 extern "C" void tts_t5_default_config(tts_t5_config * c) {
@@ -68,100 +57,45 @@ extern "C" void tts_t5_default_config(tts_t5_config * c) {
     c->pad_ = 0;
 }
 
-// Tensor names are the GGUF names without the "t5encoder." prefix (t5/model.cpp:6-25).
-static std::string gguf_name(const tts_tensor * t) { return std::string("t5encoder.") + t->name; }
-
-static tts_tensor * wnew(tts_t5 * p, std::vector<t5_wspec> & specs, int type, int64_t ne0, int64_t ne1, int kind, const std::string & name) {
-    if (p->gguf) {  // the file decides the storage type
-        const int64_t i = tts_gguf_find_tensor(p->gguf, ("t5encoder." + name).c_str());
-        if (i >= 0) type = tts_gguf_tensor_type(p->gguf, i);
-    }
-    tts_tensor * t = ne1 > 1 ? tg::new_tensor_2d(p->wctx, type, ne0, ne1) : tg::new_tensor_1d(p->wctx, type, ne0);
-    tg::set_name(t, name);
-    t->flags |= tg::TG_FLAG_PERSIST;
-    specs.push_back({t, kind, p->cfg.seed ^ (p->tensor_index++)});
-    return t;
+// kind: 0 = matrix, 1 = norm weight (~1), 2 = bias (~0), 3 = embedding, 4 = relative attention bias (values
+// that move the softmax); 1..3 only as F32, any other storage type is a matrix.  With a file attached it
+// decides the storage type.
+static tts_tensor * wnew(tts_t5 * p, int type, int64_t ne0, int64_t ne1, int kind, const std::string & name) {
+    type = p->w.file_type(name, type);
+    const weight_fill fill = kind == 4                         ? weight_fill::uniform(2.0f, 0.0f)
+                             : type != TTS_TYPE_F32 || kind == 0 ? weight_fill::matrix(kind == 3 ? 0.25f : 0.05f)
+                             : kind == 1                       ? weight_fill::uniform(0.1f, 1.0f)
+                             : kind == 2                       ? weight_fill::uniform(0.02f, 0.0f)
+                                                               : weight_fill::uniform(0.5f, 0.0f);
+    return p->w.add(type, ne0, ne1, 1, name, fill, p->cfg.seed ^ p->w.index());
 }
 
-static void declare_weights(tts_t5 * p, std::vector<t5_wspec> & specs) {
+static void declare_weights(tts_t5 * p) {
     const auto & cf = p->cfg;
+    p->w.prefix = "t5encoder.";  // t5/model.cpp:6-25
     const int64_t E = cf.hidden_size, A = (int64_t)cf.n_attn_heads * cf.head_size, F = cf.ffn_size;
     const int wt = cf.weight_type;
-    p->embd = wnew(p, specs, wt, E, cf.vocab_size, 3, "token_embd");
-    p->rel_bias = wnew(p, specs, TTS_TYPE_F32, cf.n_attn_heads, cf.relative_attn_buckets, 4, "enc.blk.0.attn_rel_b");
+    p->embd = wnew(p, wt, E, cf.vocab_size, 3, "token_embd");
+    p->rel_bias = wnew(p, TTS_TYPE_F32, cf.n_attn_heads, cf.relative_attn_buckets, 4, "enc.blk.0.attn_rel_b");
     p->layers.resize(cf.n_layers);
     for (int l = 0; l < cf.n_layers; ++l) {
         t5_layer & L = p->layers[l];
         const std::string pre = "enc.blk." + std::to_string(l);
-        L.attn_norm = wnew(p, specs, TTS_TYPE_F32, E, 1, 1, pre + ".attn_norm");
-        L.q = wnew(p, specs, wt, E, A, 0, pre + ".attn_q");
-        L.k = wnew(p, specs, wt, E, A, 0, pre + ".attn_k");
-        L.v = wnew(p, specs, wt, E, A, 0, pre + ".attn_v");
-        L.o = wnew(p, specs, wt, A, E, 0, pre + ".attn_o");
-        L.mlp_norm = wnew(p, specs, TTS_TYPE_F32, E, 1, 1, pre + ".ffn_norm");
-        L.wi_0 = wnew(p, specs, wt, E, F, 0, pre + ".ffn_up");    // the GELU branch
-        L.wi_1 = wnew(p, specs, wt, E, F, 0, pre + ".ffn_gate");
-        L.wo = wnew(p, specs, wt, F, E, 0, pre + ".ffn_down");
+        L.attn_norm = wnew(p, TTS_TYPE_F32, E, 1, 1, pre + ".attn_norm");
+        L.q = wnew(p, wt, E, A, 0, pre + ".attn_q");
+        L.k = wnew(p, wt, E, A, 0, pre + ".attn_k");
+        L.v = wnew(p, wt, E, A, 0, pre + ".attn_v");
+        L.o = wnew(p, wt, A, E, 0, pre + ".attn_o");
+        L.mlp_norm = wnew(p, TTS_TYPE_F32, E, 1, 1, pre + ".ffn_norm");
+        L.wi_0 = wnew(p, wt, E, F, 0, pre + ".ffn_up");    // the GELU branch
+        L.wi_1 = wnew(p, wt, E, F, 0, pre + ".ffn_gate");
+        L.wo = wnew(p, wt, F, E, 0, pre + ".ffn_down");
     }
-    p->out_norm = wnew(p, specs, TTS_TYPE_F32, E, 1, 1, "enc.final_layer_norm");
+    p->out_norm = wnew(p, TTS_TYPE_F32, E, 1, 1, "enc.final_layer_norm");
     if (cf.has_down_proj) {
-        p->down_proj = wnew(p, specs, wt, E, cf.output_size, 0, "down_proj");
-        p->down_proj_bias = wnew(p, specs, TTS_TYPE_F32, cf.output_size, 1, 2, "down_proj_bias");
+        p->down_proj = wnew(p, wt, E, cf.output_size, 0, "down_proj");
+        p->down_proj_bias = wnew(p, TTS_TYPE_F32, cf.output_size, 1, 2, "down_proj_bias");
     }
-}
-
-// The synthetic bytes tts_t5_create uploads for a spec (host).
-static void synth_host(const t5_wspec & s, std::vector<char> & host) {
-    const tts_tensor * t = s.t;
-    host.resize(tg::nbytes(t));
-    const int64_t K = t->ne[0], rows = tg::nelements(t) / t->ne[0];
-    const size_t n = (size_t)(K * rows);
-    if (t->type == TTS_TYPE_F32 && s.kind == 1) synth_f32((float *)host.data(), n, s.seed, 0.1f, 1.0f);
-    else if (t->type == TTS_TYPE_F32 && s.kind == 2) synth_f32((float *)host.data(), n, s.seed, 0.02f, 0.0f);
-    else if (t->type == TTS_TYPE_F32 && s.kind == 3) synth_f32((float *)host.data(), n, s.seed, 0.5f, 0.0f);
-    else if (s.kind == 4) synth_f32((float *)host.data(), n, s.seed, 2.0f, 0.0f);  // biases that move the softmax
-    else synth_fill(t->type, host.data(), rows, K, s.seed, s.kind == 3 ? 0.25f : 0.05f);
-}
-
-static const void * gguf_source(const tts_gguf * g, const std::string & fname, const tts_tensor * t) {
-    const int64_t i = tts_gguf_find_tensor(g, fname.c_str());
-    if (i < 0) {
-        fprintf(stderr, "gguf: tensor '%s' is missing\n", fname.c_str());
-        return nullptr;
-    }
-    int64_t ne[4];
-    tts_gguf_tensor_ndims(g, i, ne);
-    if (tts_gguf_tensor_type(g, i) != t->type || tts_gguf_tensor_size(g, i) != tg::nbytes(t) || ne[0] != t->ne[0] || ne[1] != t->ne[1]) {
-        fprintf(stderr, "gguf: tensor '%s' has type %d [%lld %lld], the runner needs type %d [%lld %lld]\n", fname.c_str(),
-                tts_gguf_tensor_type(g, i), (long long)ne[0], (long long)ne[1], t->type, (long long)t->ne[0], (long long)t->ne[1]);
-        return nullptr;
-    }
-    return tts_gguf_tensor_data(g, i);
-}
-
-static bool upload_weights(tts_t5 * p, std::vector<t5_wspec> & specs) {
-    size_t total = 0;
-    for (auto & s : specs) total += (tg::nbytes(s.t) + 255) & ~(size_t)255;
-    p->wbuf = p->be.alloc(p->be.ctx, total);
-    if (!p->wbuf) return false;
-    p->wbytes = total;
-    size_t off = 0;
-    std::vector<char> host;
-    for (auto & s : specs) {
-        tts_tensor * t = s.t;
-        t->data = (char *)p->wbuf + off;
-        off += (tg::nbytes(t) + 255) & ~(size_t)255;
-        const void * src;
-        if (p->gguf) {
-            src = gguf_source(p->gguf, gguf_name(t), t);
-            if (!src) return false;
-        } else {
-            synth_host(s, host);
-            src = host.data();
-        }
-        if (p->be.set_tensor(p->be.ctx, t, src) != 0) return false;
-    }
-    return true;
 }
 
 static tts_t5 * t5_create(const tts_backend_iface * be, const tts_t5_config * cfg, const tts_gguf * g) {
@@ -177,16 +111,13 @@ static tts_t5 * t5_create(const tts_backend_iface * be, const tts_t5_config * cf
     p->cfg = cf;
     if (!cf.has_down_proj) p->cfg.output_size = cf.hidden_size;
     p->be = *be;
-    p->gguf = g;
-    std::vector<t5_wspec> specs;
-    declare_weights(p, specs);
-    for (auto & s : specs) p->wlist.push_back(s.t);
-    if (!upload_weights(p, specs)) {
+    p->w.attach(g);
+    declare_weights(p);
+    if (!p->w.upload(p->be)) {
         fprintf(stderr, "t5: weight allocation/upload failed\n");
         tts_t5_free(p);
         return nullptr;
     }
-    p->gguf = nullptr;
     // the worst-case graph (t5_runner::prepare_post_load): a few [width, ctx] activations and the
     // [ctx, ctx, heads] bias and score tensors
     const size_t T = (size_t)p->cfg.max_context_length;
@@ -205,7 +136,7 @@ extern "C" tts_t5 * tts_t5_create(const tts_backend_iface * be, const tts_t5_con
 extern "C" void tts_t5_free(tts_t5 * p) {
     if (!p) return;
     if (p->arena) p->be.free(p->be.ctx, p->arena);
-    if (p->wbuf) p->be.free(p->be.ctx, p->wbuf);
+    p->w.release(p->be);
     delete p;
 }
 
@@ -311,82 +242,56 @@ extern "C" int tts_t5_encode(tts_t5 * p, const int32_t * tokens, int32_t n, floa
 
 extern "C" int32_t tts_t5_output_size(const tts_t5 * p) { return p ? p->cfg.output_size : 0; }
 extern "C" int32_t tts_t5_last_graph_nodes(const tts_t5 * p) { return p ? p->last_nodes : 0; }
-extern "C" uint64_t tts_t5_weight_bytes(const tts_t5 * p) { return p ? p->wbytes : 0; }
-extern "C" int32_t tts_t5_n_weights(const tts_t5 * p) { return p ? (int32_t)p->wlist.size() : 0; }
+extern "C" uint64_t tts_t5_weight_bytes(const tts_t5 * p) { return p ? p->w.wbytes : 0; }
+extern "C" int32_t tts_t5_n_weights(const tts_t5 * p) { return p ? p->w.size() : 0; }
 extern "C" uint64_t tts_t5_weight(tts_t5 * p, int32_t i, char * name, uint64_t name_cap, int64_t * ne, int32_t * type, void * dst, uint64_t cap) {
-    if (!p || i < 0 || i >= (int32_t)p->wlist.size()) return 0;
-    return tg::weight_out(p->be, p->wlist[i], name, name_cap, ne, type, dst, cap);
+    const tts_tensor * t = p ? p->w.tensor(i) : nullptr;
+    return t ? tg::weight_out(p->be, t, name, name_cap, ne, type, dst, cap) : 0;
 }
-extern "C" tts_tensor * const * tts_t5_graph(const tts_t5 * p, int32_t * n_nodes) {
-    if (n_nodes) *n_nodes = p ? (int32_t)p->gctx.nodes.size() : 0;
-    return p ? p->gctx.nodes.data() : nullptr;
-}
+extern "C" tts_tensor * const * tts_t5_graph(const tts_t5 * p, int32_t * n_nodes) { return tg::graph_out(p ? &p->gctx : nullptr, n_nodes); }
 
-// Debug: a named node ("pos_bias", "t5_output") or input ("pos_bucket") of the last graph.
+// Debug: a named node ("pos_bias", "t5_output": the last one of that name) or input ("pos_bucket") of the last graph.
 extern "C" uint64_t tts_t5_get_node(tts_t5 * p, const char * name, void * dst, uint64_t cap) {
     if (!p || !name) return 0;
     const tts_tensor * hit = nullptr;
     for (auto * t : p->gctx.nodes)
         if (strcmp(t->name, name) == 0) hit = t;
     if (!hit && p->in_pos_bucket && strcmp(p->in_pos_bucket->name, name) == 0 && p->last_nodes) hit = p->in_pos_bucket;
-    if (!hit || !tg::is_contiguous(hit)) return 0;
-    const size_t nb = tg::nbytes(hit);
-    if (!dst || nb > cap) return nb;
-    if (p->be.get(p->be.ctx, dst, hit->data, nb) != 0) return 0;
-    return nb;
+    return hit ? tg::tensor_out(p->be, hit, dst, cap) : 0;
 }
 
 // Debug: node i of the last graph: op / type / ne; copies its bytes when contiguous (returns size).
 extern "C" uint64_t tts_t5_node(tts_t5 * p, int32_t i, int32_t * op, int32_t * type, int64_t * ne, void * dst, uint64_t cap) {
-    if (!p || i < 0 || i >= (int32_t)p->gctx.nodes.size()) return 0;
-    const tts_tensor * t = p->gctx.nodes[i];
-    *op = t->op;
-    *type = t->type;
-    for (int k = 0; k < 4; ++k) ne[k] = t->ne[k];
-    if (!tg::is_contiguous(t) || !dst) return 0;
-    const size_t nb = tg::nbytes(t);
-    if (nb > cap) return 0;
-    if (p->be.get(p->be.ctx, dst, t->data, nb) != 0) return 0;
-    return nb;
+    return p ? tg::node_out(p->be, p->gctx.nodes, i, op, type, ne, dst, cap) : 0;
 }
 
 // ---- GGUF (t5_encoder::prep_constants / assign_weight, t5/model.cpp:27-110) ----
-static void gguf_u32(const tts_gguf * g, const char * key, int32_t * out) {
-    const int64_t i = tts_gguf_find_key(g, key);
-    uint32_t v;
-    if (i >= 0 && tts_gguf_get_u32(g, i, &v)) *out = (int32_t)v;
-}
-
 extern "C" int tts_t5_config_from_gguf(const tts_gguf * g, tts_t5_config * c) {
     if (!g || !c) return TTS_STATUS_BAD_ARG;
     if (tts_gguf_find_key(g, "t5encoder.vocab_size") < 0) {
         fprintf(stderr, "gguf: key 't5encoder.vocab_size' must be specified\n");
         return TTS_STATUS_BAD_ARG;
     }
-    gguf_u32(g, "t5encoder.vocab_size", &c->vocab_size);
-    gguf_u32(g, "t5encoder.block_count", &c->n_layers);
-    gguf_u32(g, "t5encoder.embedding_length", &c->hidden_size);
-    gguf_u32(g, "t5encoder.attention.head_count", &c->n_attn_heads);
-    gguf_u32(g, "t5encoder.context_length", &c->max_context_length);
-    gguf_u32(g, "t5encoder.output_size", &c->output_size);
-    gguf_u32(g, "tokenizer.ggml.eos_token_id", &c->eos_token_id);
+    gguf_first_u32(g, {"t5encoder.vocab_size"}, &c->vocab_size);
+    gguf_first_u32(g, {"t5encoder.block_count"}, &c->n_layers);
+    gguf_first_u32(g, {"t5encoder.embedding_length"}, &c->hidden_size);
+    gguf_first_u32(g, {"t5encoder.attention.head_count"}, &c->n_attn_heads);
+    gguf_first_u32(g, {"t5encoder.context_length"}, &c->max_context_length);
+    gguf_first_u32(g, {"t5encoder.output_size"}, &c->output_size);
+    gguf_first_u32(g, {"tokenizer.ggml.eos_token_id"}, &c->eos_token_id);
     // sizes and types the tensors themselves carry
-    const int64_t up = tts_gguf_find_tensor(g, "t5encoder.enc.blk.0.ffn_up");
-    const int64_t aq = tts_gguf_find_tensor(g, "t5encoder.enc.blk.0.attn_q");
-    const int64_t rb = tts_gguf_find_tensor(g, "t5encoder.enc.blk.0.attn_rel_b");
-    if (up < 0 || aq < 0 || rb < 0) {
+    const int64_t ffn = gguf_tensor_dim(g, "t5encoder.enc.blk.0.ffn_up", 1);
+    const int64_t attn = gguf_tensor_dim(g, "t5encoder.enc.blk.0.attn_q", 1);
+    const int64_t buckets = gguf_tensor_dim(g, "t5encoder.enc.blk.0.attn_rel_b", 1);
+    if (ffn < 0 || attn < 0 || buckets < 0) {
         fprintf(stderr, "gguf: t5encoder tensors missing\n");
         return TTS_STATUS_BAD_ARG;
     }
-    int64_t ne[4];
-    tts_gguf_tensor_ndims(g, up, ne);
-    c->ffn_size = (int32_t)ne[1];
-    tts_gguf_tensor_ndims(g, aq, ne);
-    if (c->n_attn_heads < 1 || ne[1] % c->n_attn_heads) return TTS_STATUS_BAD_ARG;
-    c->head_size = (int32_t)(ne[1] / c->n_attn_heads);
-    tts_gguf_tensor_ndims(g, rb, ne);
-    c->relative_attn_buckets = (int32_t)ne[1];
-    c->weight_type = tts_gguf_tensor_type(g, aq);
+    c->ffn_size = (int32_t)ffn;
+    if (c->n_attn_heads < 1 || attn % c->n_attn_heads) return TTS_STATUS_BAD_ARG;
+    c->head_size = (int32_t)(attn / c->n_attn_heads);
+    c->relative_attn_buckets = (int32_t)buckets;
+    c->weight_type = tts_gguf_tensor_type(g, tts_gguf_find_tensor(g, "t5encoder.enc.blk.0.attn_q"));
     c->has_down_proj = tts_gguf_find_tensor(g, "t5encoder.down_proj") >= 0 ? 1 : 0;
     if (c->weight_type != TTS_TYPE_F32 && c->weight_type != TTS_TYPE_F16) {
         fprintf(stderr, "gguf: quantized t5encoder weights are not supported\n");
@@ -404,8 +309,7 @@ extern "C" int tts_t5_write_synthetic_gguf(const tts_t5_config * cfg, const char
     if (!cfg || !path) return TTS_STATUS_BAD_ARG;
     tts_t5 p;  // declarations only: no backend, no buffers
     p.cfg = *cfg;
-    std::vector<t5_wspec> specs;
-    declare_weights(&p, specs);
+    declare_weights(&p);
     tts_gguf_writer * w = tts_gguf_writer_new();
     const auto & c = *cfg;
     tts_gguf_set_str(w, "general.architecture", "t5encoder");
@@ -416,14 +320,7 @@ extern "C" int tts_t5_write_synthetic_gguf(const tts_t5_config * cfg, const char
     tts_gguf_set_u32(w, "t5encoder.vocab_size", (uint32_t)c.vocab_size);
     if (c.has_down_proj) tts_gguf_set_u32(w, "t5encoder.output_size", (uint32_t)c.output_size);
     tts_gguf_set_u32(w, "tokenizer.ggml.eos_token_id", (uint32_t)c.eos_token_id);
-    int st = TTS_STATUS_SUCCESS;
-    std::vector<char> host;
-    for (auto & s : specs) {
-        synth_host(s, host);
-        const int nd = s.t->ne[1] > 1 ? 2 : 1;
-        st = tts_gguf_add_tensor(w, gguf_name(s.t).c_str(), s.t->type, nd, s.t->ne, host.data(), host.size());
-        if (st != TTS_STATUS_SUCCESS) break;
-    }
+    int st = p.w.write(w);
     if (st == TTS_STATUS_SUCCESS) st = tts_gguf_writer_write(w, path);
     tts_gguf_writer_free(w);
     return st;

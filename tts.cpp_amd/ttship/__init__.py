@@ -675,6 +675,59 @@ def runner_weights(n_fn, w_fn, ptr):
     return out
 
 
+class _Runner:
+    """What the runner classes share, over the exported tts_<PREFIX>_* functions: self.L is the library and
+    self.ptr the runner.  A method whose function a runner does not export is not available on it."""
+    PREFIX = None
+    TYPED_WEIGHTS = True  # tts_<PREFIX>_weight reports the ggml type and returns the stored bytes; else f32 values
+
+    def _fn(self, name):
+        return getattr(self.L, f"{self.PREFIX}_{name}")
+
+    def weight_bytes(self):
+        return self._fn("weight_bytes")(self.ptr)
+
+    def weights(self):
+        """{name: float32 array shaped like torch (reversed ggml ne, leading 1s dropped)}; quantized weights are skipped."""
+        n_fn, w_fn = self._fn("n_weights"), self._fn("weight")
+        if self.TYPED_WEIGHTS:
+            return runner_weights(n_fn, w_fn, self.ptr)
+        return runner_weights(n_fn, lambda ptr, i, name, cap, ne, ty, dst, n: w_fn(ptr, i, name, cap, ne, dst, n), self.ptr)
+
+    def plan_stats(self, mask=None):
+        """Fusion coverage of the last graph (no device needed): {item kind: count, "unfused": n}."""
+        n = ctypes.c_int32()
+        p = self._fn("graph")(self.ptr, ctypes.byref(n))
+        return plan_stats(p, n.value, FUSE_ALL if mask is None else mask)
+
+    def node(self, i, cap=1 << 26):
+        """(op, type, ne, float32 array or None) of node i of the last graph (debugging)."""
+        import numpy as np
+        op, ty = ctypes.c_int32(), ctypes.c_int32()
+        ne = (ctypes.c_int64 * 4)()
+        buf = np.empty(cap // 4, dtype=np.float32)
+        n = self._fn("node")(self.ptr, i, ctypes.byref(op), ctypes.byref(ty), ne, buf.ctypes.data, cap)
+        data = buf[: n // 4].copy() if n else None
+        return OPS[op.value], ty.value, tuple(ne), data
+
+    def named(self, name, dtype="float32", lead=()):
+        """Flat values of a named tensor of the last graph, or None (lead: arguments tts_<PREFIX>_get_node takes
+        before the name)."""
+        import numpy as np
+        get = self._fn("get_node")
+        n = get(self.ptr, *lead, name.encode(), None, 0)
+        if not n:
+            return None
+        a = np.empty(n // 4, dtype=dtype)
+        get(self.ptr, *lead, name.encode(), a.ctypes.data, n)
+        return a
+
+    def close(self):
+        if self.ptr:
+            self._fn("free")(self.ptr)
+            self.ptr = None
+
+
 def coalesce_stats(device=0):
     """Step-coalescer counters of `device` (tts_hip_coalesce_stats)."""
     out = (ctypes.c_int64 * 11)()
@@ -703,8 +756,9 @@ def dia_config(**kw):
     return cfg
 
 
-class Dia:
+class Dia(_Runner):
     """Dia-1.6B runner (encoder step + CFG decoder steps) over a backend vtable."""
+    PREFIX = "tts_dia"
 
     def __init__(self, iface, cfg):
         self.L = lib()
@@ -755,22 +809,6 @@ class Dia:
     def position(self):
         return self.L.tts_dia_position(self.ptr)
 
-    def weight_bytes(self):
-        return self.L.tts_dia_weight_bytes(self.ptr)
-
-    def weights(self):
-        return runner_weights(self.L.tts_dia_n_weights, self.L.tts_dia_weight, self.ptr)
-
-    def plan_stats(self, mask=None):
-        n = ctypes.c_int32()
-        p = self.L.tts_dia_graph(self.ptr, ctypes.byref(n))
-        return plan_stats(p, n.value, FUSE_ALL if mask is None else mask)
-
-    def close(self):
-        if self.ptr:
-            self.L.tts_dia_free(self.ptr)
-            self.ptr = None
-
 
 def t5_config(**kw):
     cfg = T5Config()
@@ -780,8 +818,9 @@ def t5_config(**kw):
     return cfg
 
 
-class T5:
+class T5(_Runner):
     """T5 voice-description encoder runner (Parler's conditional prompt) over a backend vtable."""
+    PREFIX = "tts_t5"
 
     def __init__(self, iface, cfg, gguf=None):
         """gguf: a Gguf file whose "t5encoder.*" tensors are the weights (cfg from t5_config_from_gguf)."""
@@ -817,43 +856,6 @@ class T5:
     def last_graph_nodes(self):
         return self.L.tts_t5_last_graph_nodes(self.ptr)
 
-    def weight_bytes(self):
-        return self.L.tts_t5_weight_bytes(self.ptr)
-
-    def weights(self):
-        return runner_weights(self.L.tts_t5_n_weights, self.L.tts_t5_weight, self.ptr)
-
-    def plan_stats(self, mask=None):
-        """Fusion coverage of the last encode graph (no device needed)."""
-        n = ctypes.c_int32()
-        p = self.L.tts_t5_graph(self.ptr, ctypes.byref(n))
-        return plan_stats(p, n.value, FUSE_ALL if mask is None else mask)
-
-    def node(self, i, cap=1 << 26):
-        """(op, type, ne, float32 array or None) of node i of the last graph (debugging)."""
-        import numpy as np
-        op, ty = ctypes.c_int32(), ctypes.c_int32()
-        ne = (ctypes.c_int64 * 4)()
-        buf = np.empty(cap // 4, dtype=np.float32)
-        n = self.L.tts_t5_node(self.ptr, i, ctypes.byref(op), ctypes.byref(ty), ne, buf.ctypes.data, cap)
-        data = buf[: n // 4].copy() if n else None
-        return OPS[op.value], ty.value, tuple(ne), data
-
-    def named(self, name, dtype="float32"):
-        """Flat values of a named tensor of the last graph ("pos_bucket" int32, "pos_bias", "t5_output"), or None."""
-        import numpy as np
-        n = self.L.tts_t5_get_node(self.ptr, name.encode(), None, 0)
-        if not n:
-            return None
-        a = np.empty(n // 4, dtype=dtype)
-        self.L.tts_t5_get_node(self.ptr, name.encode(), a.ctypes.data, n)
-        return a
-
-    def close(self):
-        if self.ptr:
-            self.L.tts_t5_free(self.ptr)
-            self.ptr = None
-
 
 def orpheus_config(**kw):
     cfg = OrpheusConfig()
@@ -863,8 +865,9 @@ def orpheus_config(**kw):
     return cfg
 
 
-class Orpheus:
+class Orpheus(_Runner):
     """Orpheus-3B decoder runner over a backend vtable (HIP, or the oracle in tests)."""
+    PREFIX = "tts_orpheus"
 
     def __init__(self, iface, cfg):
         self.L = lib()
@@ -912,23 +915,6 @@ class Orpheus:
     def last_graph_nodes(self):
         return self.L.tts_orpheus_last_graph_nodes(self.ptr)
 
-    def weight_bytes(self):
-        return self.L.tts_orpheus_weight_bytes(self.ptr)
-
-    def weights(self):
-        return runner_weights(self.L.tts_orpheus_n_weights, self.L.tts_orpheus_weight, self.ptr)
-
-    def plan_stats(self, mask=None):
-        """Fusion coverage of the last step graph (no device needed)."""
-        n = ctypes.c_int32()
-        p = self.L.tts_orpheus_graph(self.ptr, ctypes.byref(n))
-        return plan_stats(p, n.value, FUSE_ALL if mask is None else mask)
-
-    def close(self):
-        if self.ptr:
-            self.L.tts_orpheus_free(self.ptr)
-            self.ptr = None
-
 
 def parler_config(**kw):
     cfg = ParlerConfig()
@@ -938,8 +924,9 @@ def parler_config(**kw):
     return cfg
 
 
-class Parler:
+class Parler(_Runner):
     """Parler-TTS decoder runner over a backend vtable (HIP, or the oracle in tests)."""
+    PREFIX = "tts_parler"
 
     def __init__(self, iface, cfg, gguf=None):
         """gguf: a Gguf file whose "decoder.*" tensors are the weights (cfg from parler_config_from_gguf)."""
@@ -1030,39 +1017,12 @@ class Parler:
     def last_graph_nodes(self):
         return self.L.tts_parler_last_graph_nodes(self.ptr)
 
-    def plan_stats(self, mask=None):
-        """Fusion coverage of the last step graph (no device needed)."""
-        n = ctypes.c_int32()
-        p = self.L.tts_parler_graph(self.ptr, ctypes.byref(n))
-        return plan_stats(p, n.value, FUSE_ALL if mask is None else mask)
-
     def host_stats(self, reset=True):
         """Mean host microseconds per step: build, alloc, set_inputs, compute enqueue, logits wait."""
         us = (ctypes.c_double * 5)()
         n = self.L.tts_parler_host_stats(self.ptr, us, 1 if reset else 0)
         names = ["build", "alloc", "set_inputs", "compute_enqueue", "logits_wait"]
         return {k: round(us[i] / max(n, 1), 1) for i, k in enumerate(names)}
-
-    def node(self, i, cap=1 << 26):
-        """(op, type, ne, float32 array or None) of node i of the last step graph (debugging)."""
-        import numpy as np
-        op, ty = ctypes.c_int32(), ctypes.c_int32()
-        ne = (ctypes.c_int64 * 4)()
-        buf = np.empty(cap // 4, dtype=np.float32)
-        n = self.L.tts_parler_node(self.ptr, i, ctypes.byref(op), ctypes.byref(ty), ne, buf.ctypes.data, cap)
-        data = buf[: n // 4].copy() if n else None
-        return OPS[op.value], ty.value, tuple(ne), data
-
-    def weight_bytes(self):
-        return self.L.tts_parler_weight_bytes(self.ptr)
-
-    def weights(self):
-        return runner_weights(self.L.tts_parler_n_weights, self.L.tts_parler_weight, self.ptr)
-
-    def close(self):
-        if self.ptr:
-            self.L.tts_parler_free(self.ptr)
-            self.ptr = None
 
 
 def dac_config(**kw):
@@ -1077,8 +1037,9 @@ def dac_config(**kw):
     return cfg
 
 
-class Dac:
+class Dac(_Runner):
     """DAC decoder runner (codec tokens -> PCM) over a backend vtable (HIP, or the oracle in tests)."""
+    PREFIX = "tts_dac"
 
     def __init__(self, iface, cfg, gguf=None):
         """gguf: a Gguf file whose "audio_encoder.*" tensors are the weights (cfg from dac_config_from_gguf)."""
@@ -1095,9 +1056,6 @@ class Dac:
     @property
     def hop(self):
         return self.L.tts_dac_hop(self.ptr)
-
-    def weights(self):
-        return runner_weights(self.L.tts_dac_n_weights, self.L.tts_dac_weight, self.ptr)
 
     def decode(self, codes):
         """codes: (T, n_codebooks) int -> (T * hop,) float32 PCM."""
@@ -1126,19 +1084,8 @@ class Dac:
     def min_gap(self):
         return self.L.tts_dac_min_gap(self.ptr)
 
-    def plan_stats(self, mask=None):
-        """Fusion coverage of the last decode graph (no device needed)."""
-        n = ctypes.c_int32()
-        p = self.L.tts_dac_graph(self.ptr, ctypes.byref(n))
-        return plan_stats(p, n.value, FUSE_ALL if mask is None else mask)
-
     def last_graph_nodes(self):
         return self.L.tts_dac_last_graph_nodes(self.ptr)
-
-    def close(self):
-        if self.ptr:
-            self.L.tts_dac_free(self.ptr)
-            self.ptr = None
 
 
 def snac_config(**kw):
@@ -1153,8 +1100,10 @@ def snac_config(**kw):
     return cfg
 
 
-class Snac:
+class Snac(_Runner):
     """SNAC decoder runner (Orpheus' three codebook streams -> 24 kHz PCM) over a backend vtable."""
+    PREFIX = "tts_snac"
+    TYPED_WEIGHTS = False
 
     def __init__(self, iface, cfg):
         self.L = lib()
@@ -1197,27 +1146,6 @@ class Snac:
         n = self.L.tts_snac_get_node(self.ptr, name.encode(), buf.ctypes.data, cap)
         return buf[: n // 4].copy() if n else None
 
-    def weights(self):
-        """{name: float32 array shaped like torch (reversed ggml ne, leading 1s dropped)}."""
-        import numpy as np
-        out = {}
-        for i in range(self.L.tts_snac_n_weights(self.ptr)):
-            name = ctypes.create_string_buffer(128)
-            ne = (ctypes.c_int64 * 4)()
-            n = self.L.tts_snac_weight(self.ptr, i, name, 128, ne, None, 0)
-            a = np.empty(n // 4, dtype=np.float32)
-            self.L.tts_snac_weight(self.ptr, i, name, 128, ne, a.ctypes.data, n)
-            shape = [int(v) for v in reversed(list(ne))]
-            while len(shape) > 1 and shape[0] == 1:
-                shape.pop(0)
-            out[name.value.decode()] = a.reshape(shape)
-        return out
-
-    def close(self):
-        if self.ptr:
-            self.L.tts_snac_free(self.ptr)
-            self.ptr = None
-
 
 def kokoro_gen_config(**kw):
     cfg = KokoroGenConfig()
@@ -1248,8 +1176,10 @@ def kokoro_config(gen=None, **kw):
     return cfg
 
 
-class Kokoro:
+class Kokoro(_Runner):
     """Kokoro-82M end to end (phoneme ids -> durations -> 24 kHz PCM) over a backend vtable."""
+    PREFIX = "tts_kokoro"
+    TYPED_WEIGHTS = False
 
     def __init__(self, iface, cfg):
         self.L = lib()
@@ -1306,31 +1236,9 @@ class Kokoro:
             raise RuntimeError(f"tts_kokoro_run failed {st}")
         return pcm[: ns.value]
 
-    def weights(self):
-        """{name: float32 array shaped like torch (reversed ggml ne, leading 1s dropped)}."""
-        import numpy as np
-        out = {}
-        for i in range(self.L.tts_kokoro_n_weights(self.ptr)):
-            name = ctypes.create_string_buffer(128)
-            ne = (ctypes.c_int64 * 4)()
-            n = self.L.tts_kokoro_weight(self.ptr, i, name, 128, ne, None, 0)
-            a = np.empty(n // 4, dtype=np.float32)
-            self.L.tts_kokoro_weight(self.ptr, i, name, 128, ne, a.ctypes.data, n)
-            shape = [int(v) for v in reversed(list(ne))]
-            while len(shape) > 1 and shape[0] == 1:
-                shape.pop(0)
-            out[name.value.decode()] = a.reshape(shape)
-        return out
-
     def node(self, name, which=1):
         """float32 values of a named node of the last duration (0) / main (1) graph, or None."""
-        import numpy as np
-        n = self.L.tts_kokoro_get_node(self.ptr, which, name.encode(), None, 0)
-        if not n:
-            return None
-        a = np.empty(n // 4, dtype=np.float32)
-        self.L.tts_kokoro_get_node(self.ptr, which, name.encode(), a.ctypes.data, n)
-        return a
+        return self.named(name, lead=(which,))
 
     def plan_stats(self, which=1, mask=None):
         n = ctypes.c_int32()
@@ -1340,14 +1248,11 @@ class Kokoro:
     def last_graph_nodes(self, which=1):
         return self.L.tts_kokoro_last_graph_nodes(self.ptr, which)
 
-    def close(self):
-        if self.ptr:
-            self.L.tts_kokoro_free(self.ptr)
-            self.ptr = None
 
-
-class KokoroGenerator:
+class KokoroGenerator(_Runner):
     """Kokoro iSTFTNet generator runner (features + F0 + style -> PCM) over a backend vtable."""
+    PREFIX = "tts_kokoro_gen"
+    TYPED_WEIGHTS = False
 
     def __init__(self, iface, cfg):
         self.L = lib()
@@ -1382,58 +1287,14 @@ class KokoroGenerator:
             raise RuntimeError(f"tts_kokoro_gen_run failed {st}")
         return pcm
 
-    def weights(self):
-        """{name: float32 array shaped like torch (reversed ggml ne, leading 1s dropped)}."""
-        import numpy as np
-        out = {}
-        for i in range(self.L.tts_kokoro_gen_n_weights(self.ptr)):
-            name = ctypes.create_string_buffer(128)
-            ne = (ctypes.c_int64 * 4)()
-            n = self.L.tts_kokoro_gen_weight(self.ptr, i, name, 128, ne, None, 0)
-            a = np.empty(n // 4, dtype=np.float32)
-            self.L.tts_kokoro_gen_weight(self.ptr, i, name, 128, ne, a.ctypes.data, n)
-            shape = [int(v) for v in reversed(list(ne))]
-            while len(shape) > 1 and shape[0] == 1:
-                shape.pop(0)
-            out[name.value.decode()] = a.reshape(shape)
-        return out
-
-    def node_at(self, i, cap=1 << 26):
-        """(op, type, ne, float32 array or None) of node i of the last graph (debugging)."""
-        import numpy as np
-        op, ty = ctypes.c_int32(), ctypes.c_int32()
-        ne = (ctypes.c_int64 * 4)()
-        buf = np.empty(cap // 4, dtype=np.float32)
-        n = self.L.tts_kokoro_gen_node(self.ptr, i, ctypes.byref(op), ctypes.byref(ty), ne, buf.ctypes.data, cap)
-        return OPS[op.value], ty.value, tuple(ne), (buf[: n // 4].copy() if n else None)
-
-    def plan_stats(self, mask=None):
-        """Fusion coverage of the last graph (no device needed): {item kind: count, "unfused": n}."""
-        return plan_stats(*self._graph(), FUSE_ALL if mask is None else mask)
-
-    def _graph(self):
-        n = ctypes.c_int32()
-        p = self.L.tts_kokoro_gen_graph(self.ptr, ctypes.byref(n))
-        return p, n.value
+    node_at = _Runner.node  # node i of the last graph; node() is the named one here
 
     def node(self, name):
         """float32 values of a named node of the last run (flat), or None."""
-        import numpy as np
-        n = self.L.tts_kokoro_gen_get_node(self.ptr, name.encode(), None, 0)
-        if not n:
-            return None
-        a = np.empty(n // 4, dtype=np.float32)
-        self.L.tts_kokoro_gen_get_node(self.ptr, name.encode(), a.ctypes.data, n)
-        return a
+        return self.named(name)
 
     def last_graph_nodes(self):
         return self.L.tts_kokoro_gen_last_graph_nodes(self.ptr)
-
-    def close(self):
-        if self.ptr:
-            self.L.tts_kokoro_gen_free(self.ptr)
-            self.ptr = None
-
 
 PLAN_KINDS = ["gemv", "attn", "ln", "lstm", "snake", "embed", "conv", "adain", "mcpy", "rint", "node", "copy"]
 

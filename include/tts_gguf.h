@@ -97,7 +97,7 @@ int tts_gguf_writer_write(const tts_gguf_writer * w, const char * path); /* 0 on
 
 /* ---- quantize tool (examples/quantize/quantize_impl.cpp) ---- */
 typedef struct tts_quantize_params {
-    int32_t quantize_type;                  /* TTS_TYPE_Q4_K, TTS_TYPE_Q8_0 or TTS_TYPE_F16 */
+    int32_t quantize_type;                  /* TTS_TYPE_Q4_K, TTS_TYPE_Q8_0, TTS_TYPE_Q5_0 or TTS_TYPE_F16 */
     int32_t quantize_output_heads;          /* quantization_params fields, same meaning */
     int32_t quantize_text_embeddings;
     int32_t quantize_cross_attn_kv;

@@ -29,7 +29,7 @@ typedef struct tts_parler_config {
     int32_t n_encode;        /* 3 ("female voice" T5 tokens) */
     int32_t prompt_vocab;    /* 32128 (T5) */
     int32_t max_positions;   /* 4102 */
-    int32_t weight_type;     /* TTS_TYPE_Q4_K for config 3 */
+    int32_t weight_type;     /* TTS_TYPE_Q4_K for config 3; Q8_0, Q5_0 (the reference's published files), F16, F32 */
     int32_t head_type;       /* TTS_TYPE_F32 (heads unquantized by default) */
     int32_t use_cross_attn;  /* 1 */
     int32_t batch;           /* independent prompts stepped in lockstep (1 = reference graph) */
@@ -200,7 +200,7 @@ typedef struct tts_dia_config {
     int32_t encoder_vocab_size;         /* 256 (byte tokens) */
     int32_t max_generation_size;        /* 3072 */
     int32_t max_encoder_context_length; /* 1024 */
-    int32_t weight_type;                /* TTS_TYPE_Q8_0 */
+    int32_t weight_type;                /* TTS_TYPE_Q8_0 (default) or TTS_TYPE_Q5_0; F16 / F32 */
     int32_t head_type;                  /* TTS_TYPE_F32 */
     float cfg_scale;                    /* 3.0 */
     uint64_t seed;                      /* synthetic weight seed base (0x5EED) */

@@ -1,7 +1,7 @@
-"""Dia-1.6B Q8_0 decode throughput on one GPU (BASELINE configs[3]): synthetic weights in the exact
+"""Dia-1.6B Q8_0 (or Q5_0) decode throughput on one GPU (BASELINE configs[3]): synthetic weights in the exact
 shapes, the encoder step over a Harvard-sentence prompt, then timed CFG decoder steps (greedy heads
 fed back).  Dia produces one 9-codebook DAC frame (512 samples at 44.1 kHz) per step.
-usage: bench_dia.py [steps] [decoder_layers]"""
+usage: bench_dia.py [steps] [decoder_layers] [--wtype q8_0|q5_0]"""
 import json
 import pathlib
 import sys
@@ -15,8 +15,16 @@ import ttship  # noqa: E402
 
 
 def main():
-    steps = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-    kw = {"n_decoder_layers": int(sys.argv[2])} if len(sys.argv) > 2 else {}
+    argv = list(sys.argv)
+    wname = "q8_0"
+    if "--wtype" in argv:  # the matrices' storage type (Dia's default is Q8_0)
+        i = argv.index("--wtype")
+        wname = argv[i + 1].lower()
+        del argv[i:i + 2]
+    wtype = {"q8_0": ttship.Q8_0, "q5_0": ttship.Q5_0}[wname]
+    steps = int(argv[1]) if len(argv) > 1 else 64
+    kw = {"n_decoder_layers": int(argv[2])} if len(argv) > 2 else {}
+    kw["weight_type"] = wtype
     be = ttship.HipBackend(0)
     d = ttship.Dia(be.iface(), ttship.dia_config(**kw))
     text = np.frombuffer(b"\x01 The birch canoe slid on the smooth planks. Glue the sheet to the dark blue background.",
@@ -35,13 +43,13 @@ def main():
     be.gemv_stats(-1, reset=True)
     for _ in range(4):
         audio = d.decode(audio).argmax(axis=1).astype(np.int32)
-    ms, n, nbytes = be.gemv_stats(ttship.Q8_0, reset=True)
+    ms, n, nbytes = be.gemv_stats(wtype, reset=True)
     be.set_option(ttship.OPT["PROFILE_GEMV"], 0)
     us = 1000 * ms / max(n, 1)
-    print(json.dumps({"workload": "Dia-1.6B Q8_0 CFG decode (BASELINE configs[3]), synthetic weights",
+    print(json.dumps({"workload": f"Dia-1.6B {wname.upper()} CFG decode (BASELINE configs[3]), synthetic weights",
                       "ms_per_step": round(1000 * dt / steps, 3), "audio_sec_per_s": round(steps * 512 / 44100 / dt, 3),
                       "encoder_step_ms": round(1000 * t_enc, 1), "weight_GB": round(d.weight_bytes() / 1e9, 3),
-                      "q8_0_gemv": {"avg_launch_us": round(us, 2), "GBps": round(nbytes / max(n, 1) / (us * 1e-6) / 1e9, 1),
+                      f"{wname}_gemv": {"avg_launch_us": round(us, 2), "GBps": round(nbytes / max(n, 1) / (us * 1e-6) / 1e9, 1),
                                     "launches": n}}), flush=True)
     d.close()
     be.close()

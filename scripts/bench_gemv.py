@@ -2,6 +2,11 @@
 
 Shapes: the Parler-mini decode matrices, Orpheus-3B / Dia sizes, at M = 1 and 8 columns.
 Prints one JSON line per shape with avg us per launch and algorithmic GB/s.
+
+bench_gemv.py q5 [reps] [rounds] [M list] [cold]: Q5_0 beside Q8_0 at the same shapes in the same run,
+interleaved -- per (shape, M) and round the slots Q8_0, Q5_0, Q8_0 again, `reps` launches each; one JSON
+line with the per-round averages, the medians and the Q8_0-against-Q8_0 spread (the margin a Q5_0 / Q8_0
+difference has to clear).
 """
 import json
 import os
@@ -27,7 +32,75 @@ SHAPES = [  # (name, type, K, N)
 ]
 
 
+Q5_SHAPES = [(1024, 1024), (1024, 4096), (4096, 1024), (2048, 2048), (2048, 8192)]  # (K, N)
+
+
+def quant_bytes(rng, wt, K, N):
+    """Random blocks of type wt with a small finite fp16 d."""
+    bs = ttship.TYPE_SIZE[wt]
+    w = rng.integers(0, 256, size=ttship.row_size(wt, K) * N, dtype=np.uint8)
+    w.reshape(-1, bs)[:, 0:2] = np.frombuffer(np.float16(1e-3).tobytes(), dtype=np.uint8)
+    return w
+
+
+def compare_q5():
+    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 40
+    rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+    mlist = [int(v) for v in sys.argv[4].split(",")] if len(sys.argv) > 4 else [1, 2, 8, 32]
+    cold = int(sys.argv[5]) if len(sys.argv) > 5 else 1
+    hip = ttship.HipBackend(0)
+    L = ttship.lib()
+    rng = np.random.default_rng(0)
+    for K, N in Q5_SHAPES:
+        dev = {}
+        for wt in (ttship.Q8_0, ttship.Q5_0):
+            w = quant_bytes(rng, wt, K, N)
+            # cold: as many copies of the LARGER (Q8_0) matrix as pass 512 MiB, the same count for both types
+            ncopy = max(1, min(64, -(-(512 << 20) // (ttship.row_size(ttship.Q8_0, K) * N)))) if cold else 1
+            dev[wt] = [hip.alloc(w.nbytes) for _ in range(ncopy)]
+            for d in dev[wt]:
+                hip.set(d, w)
+        for M in mlist:
+            x = rng.standard_normal((M, K)).astype(np.float32)
+            dx, dy = hip.alloc(x.nbytes), hip.alloc(4 * M * N)
+            hip.set(dx, x)
+
+            def slot(wt, n):
+                for c in range(n):
+                    L.tts_hip_gemv_ex(hip.ptr, wt, dev[wt][c % len(dev[wt])], dx, dy, K, N, M, 0)
+
+            for wt in dev:
+                slot(wt, 3)
+            hip.sync()
+            hip.set_option(ttship.OPT["PROFILE_GEMV"], 1)
+            us = {"q8_0_a": [], "q5_0": [], "q8_0_b": []}
+            for _ in range(rounds):
+                for key, wt in (("q8_0_a", ttship.Q8_0), ("q5_0", ttship.Q5_0), ("q8_0_b", ttship.Q8_0)):
+                    hip.gemv_stats(-1, reset=True)
+                    slot(wt, reps)
+                    ms, n, _ = hip.gemv_stats(wt, reset=True)
+                    assert n == reps, (n, reps)
+                    us[key].append(round(1000.0 * ms / n, 2))
+            hip.set_option(ttship.OPT["PROFILE_GEMV"], 0)
+            med = {k: float(np.median(v)) for k, v in us.items()}
+            q8 = 0.5 * (med["q8_0_a"] + med["q8_0_b"])
+            b8, b5 = ttship.row_size(ttship.Q8_0, K) * N, ttship.row_size(ttship.Q5_0, K) * N
+            print(json.dumps({"K": K, "N": N, "M": M, "cold": cold, "reps": reps, "us_per_round": us, "median_us": med,
+                              "q8_0_vs_q8_0_spread_us": round(max(abs(a - b) for a, b in zip(us["q8_0_a"], us["q8_0_b"])), 2),
+                              "q5_0_over_q8_0": round(med["q5_0"] / q8, 3), "bytes_ratio": round(b5 / b8, 3),
+                              "q8_0_weight_GBps": round(b8 / (q8 * 1e-6) / 1e9, 1),
+                              "q5_0_weight_GBps": round(b5 / (med["q5_0"] * 1e-6) / 1e9, 1)}), flush=True)
+            hip.free(dx)
+            hip.free(dy)
+        for ds in dev.values():
+            for d in ds:
+                hip.free(d)
+    hip.close()
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "q5":
+        return compare_q5()
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 50
     mlist = [int(v) for v in sys.argv[2].split(",")] if len(sys.argv) > 2 else [1, 8]
     tiled = int(sys.argv[3]) if len(sys.argv) > 3 else 0  # 1: Q4_K in the tile layout (matrix-core kernel)

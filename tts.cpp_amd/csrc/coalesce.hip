@@ -227,6 +227,10 @@ void copy_options(tts_hip_backend * d, const tts_hip_backend * s) {
     d->gemv_q80_slab = s->gemv_q80_slab;
     d->gemv_q80_rw = s->gemv_q80_rw;
     d->gemm_q8_staged = s->gemm_q8_staged;
+    d->gemv_q50_slab = s->gemv_q50_slab;
+    d->gemv_q50_rw = s->gemv_q50_rw;
+    d->gemm_q5 = s->gemm_q5;
+    d->gemm_q5_staged = s->gemm_q5_staged;
     d->gemv_kr_ink = s->gemv_kr_ink;
     d->gemm_kr_ct2 = s->gemm_kr_ct2;
     d->gemm_kr_xcd = s->gemm_kr_xcd;

@@ -113,7 +113,8 @@ bool is_gemv(const tts_tensor * n) {
         return false;
     switch (a->type) {
         case TTS_TYPE_Q4_K: return a->ne[0] % 256 == 0;
-        case TTS_TYPE_Q8_0: return a->ne[0] % 32 == 0;
+        case TTS_TYPE_Q8_0:
+        case TTS_TYPE_Q5_0: return a->ne[0] % 32 == 0;
         case TTS_TYPE_F32:
         case TTS_TYPE_F16: return a->ne[0] % 4 == 0 && (b->nb[1] % 16) == 0 && ((uintptr_t)b->data % 16) == 0;
         default: return false;
@@ -482,7 +483,7 @@ struct Planner {
         }
     }
 
-    // An LN item directly followed by the Q4_K GEMV item (or Q8_0 GEMV item of <= 8 columns) that
+    // An LN item directly followed by the Q4_K GEMV item (or Q8_0 / Q5_0 GEMV item of <= 8 columns) that
     // reads its output becomes that GEMV's prologue (every workgroup normalizes + quantizes the
     // activation itself; workgroup 0 still writes the LN output tensor).
     void fuse_ln_into_gemv() {
@@ -496,7 +497,7 @@ struct Planner {
             if (G.kind != Item::GEMV || G.ln || G.mms[0]->src[1] != L.dst) continue;
             const int wt = G.mms[0]->src[0]->type;
             const tts_tensor * B = G.mms[0]->src[1];
-            if (wt != TTS_TYPE_Q4_K && !(wt == TTS_TYPE_Q8_0 && q80pro && B->ne[1] * B->ne[2] * B->ne[3] <= 8)) continue;
+            if (wt != TTS_TYPE_Q4_K && !(wtype_q80_act(wt) && q80pro && B->ne[1] * B->ne[2] * B->ne[3] <= 8)) continue;
             const int64_t K = L.dst->ne[0];
             if (K % 256 || K > 4096) continue;
             if (((uintptr_t)L.w->data & 15) || (L.b && ((uintptr_t)L.b->data & 15)) || (L.dst->nb[1] & 15)) continue;
@@ -672,7 +673,7 @@ struct Planner {
         return true;
     }
 
-    // SwiGLU MLP on Q8_0 weights (Dia model.cpp:358): MUL(UNARY SILU(MUL_MAT(gate, x)), MUL_MAT(up, y)).
+    // SwiGLU MLP on Q8_0 (or Q5_0) weights (Dia model.cpp:358): MUL(UNARY SILU(MUL_MAT(gate, x)), MUL_MAT(up, y)).
     // The gate product runs alone and is stored; the up product's epilogue reads it back and writes
     // silu(gate) * up to the MUL's output (EPI_SILU_MUL), so the SILU and MUL launches and their
     // tensors disappear.  Needs the gate product first in node order, every node between the up
@@ -680,13 +681,13 @@ struct Planner {
     // MUL's output disjoint from (or exactly) the gate product and disjoint from the up product's src1.
     bool try_silu_mul(int i) {
         const tts_tensor * G = nodes[i];
-        if (G->src[0]->type != TTS_TYPE_Q8_0) return false;
+        if (!wtype_q80_act(G->src[0]->type)) return false;
         const tts_tensor * S = sole_consumer(G);
         if (!S || S->op != TTS_OP_UNARY || S->op_params[0] != TTS_UNARY_SILU || S->src[0] != G) return false;
         const tts_tensor * E = sole_consumer(S);
         if (!E || E->op != TTS_OP_MUL || E->src[0] != S) return false;
         const tts_tensor * U = E->src[1];
-        if (!U || U->op != TTS_OP_MUL_MAT || uses[U] != 1 || !is_gemv(U) || U->src[0]->type != TTS_TYPE_Q8_0) return false;
+        if (!U || U->op != TTS_OP_MUL_MAT || uses[U] != 1 || !is_gemv(U) || U->src[0]->type != G->src[0]->type) return false;
         if (E->type != TTS_TYPE_F32 || !contiguous(E) || !contiguous(G) || !contiguous(S) || !contiguous(U)) return false;
         for (int d = 0; d < 4; ++d)
             if (E->ne[d] != G->ne[d] || U->ne[d] != G->ne[d] || S->ne[d] != G->ne[d]) return false;
@@ -1580,7 +1581,7 @@ struct Planner {
         auto leaf_ok = [&](const tts_tensor * g) {
             if (g->op != TTS_OP_GET_ROWS || sole_consumer(g) != a || g->type != TTS_TYPE_F32) return false;
             const tts_tensor *tab = g->src[0], *idx = g->src[1];
-            if (tab->type != TTS_TYPE_F32 && tab->type != TTS_TYPE_F16 && tab->type != TTS_TYPE_Q8_0 && tab->type != TTS_TYPE_Q4_K) return false;
+            if (tab->type != TTS_TYPE_F32 && tab->type != TTS_TYPE_F16 && tab->type != TTS_TYPE_Q8_0 && tab->type != TTS_TYPE_Q5_0 && tab->type != TTS_TYPE_Q4_K) return false;
             if (idx->type != TTS_TYPE_I32 || idx->ne[1] * idx->ne[2] * idx->ne[3] != 1 || (idx->nb[0] % 4)) return false;
             if (tab->ne[0] != root->ne[0] || g->ne[0] != root->ne[0] || tab->ne[2] * tab->ne[3] != 1) return false;
             const int64_t rows = g->ne[1] * g->ne[2] * g->ne[3], M = root->ne[1] * root->ne[2] * root->ne[3];
@@ -2053,7 +2054,7 @@ static int prepare_act(tts_hip_backend * be, int wtype, const float * x, int64_t
         out.vtype = TTS_TYPE_F32;
         return 0;
     }
-    const int vt = wtype == TTS_TYPE_Q4_K ? TTS_TYPE_Q8_K : wtype;
+    const int vt = wtype == TTS_TYPE_Q4_K ? TTS_TYPE_Q8_K : wtype == TTS_TYPE_Q5_0 ? TTS_TYPE_Q8_0 : wtype;  // vec_dot_type
     const bool hit = aq.src == x && aq.K == K && aq.M == M && aq.vtype == vt && aq.graph_epoch == be->graph_epoch;
     if (!hit) {
         if (!ensure_scratch(be, act_quant_bytes(wtype, K, M))) return TTS_STATUS_ALLOC_FAILED;
@@ -2221,8 +2222,8 @@ static int run_gemv_item(tts_hip_backend * be, const Item & it, const Item * xat
         j.res = (const float *)it.res->data;
         j.rcs = (int64_t)(it.res->nb[1] / 4);
     }
-    // Q8_0 with <= 8 columns (K % 256 == 0): the same prologue, writing Q8_0 blocks (k_gemv_q8_0<MC, PRO>)
-    const bool q80pro = j.wtype == TTS_TYPE_Q8_0 && j.K % QK_K == 0 && j.M <= 8 && (it.ln || be->gemv_q80_pro);
+    // Q8_0 / Q5_0 with <= 8 columns (K % 256 == 0): the same prologue, writing Q8_0 blocks (k_gemv_q8_0 / q5_0<MC, PRO>)
+    const bool q80pro = wtype_q80_act(j.wtype) && j.K % QK_K == 0 && j.M <= 8 && (it.ln || be->gemv_q80_pro);
     if (j.wtype == TTS_TYPE_Q4_K || q80pro) {
         // the kernel quantizes (and normalizes) src1 itself in every workgroup
         j.pro = it.ln ? PRO_LN : PRO_QUANT;
@@ -3257,8 +3258,8 @@ extern "C" int tts_hip_gemv_res(tts_hip_backend_t be, int type, const void * w, 
     if (!be) return TTS_STATUS_BAD_ARG;
     if ((wflags & TTS_FLAG_TILED) && (type != TTS_TYPE_Q4_K || N % 4)) return TTS_STATUS_BAD_ARG;
     if (type == TTS_TYPE_Q4_K && K % 256) return TTS_STATUS_BAD_ARG;
-    if (type == TTS_TYPE_Q8_0 && K % 32) return TTS_STATUS_BAD_ARG;
-    if (type != TTS_TYPE_Q4_K && type != TTS_TYPE_Q8_0 && type != TTS_TYPE_F16 && type != TTS_TYPE_F32) return TTS_STATUS_UNSUPPORTED;
+    if (tts::wtype_q80_act(type) && K % 32) return TTS_STATUS_BAD_ARG;
+    if (type != TTS_TYPE_Q4_K && type != TTS_TYPE_Q8_0 && type != TTS_TYPE_Q5_0 && type != TTS_TYPE_F16 && type != TTS_TYPE_F32) return TTS_STATUS_UNSUPPORTED;
     if ((type == TTS_TYPE_F32 || type == TTS_TYPE_F16) && K % 4) return TTS_STATUS_BAD_ARG;
     hipSetDevice(be->device);
     GemvJob j;
@@ -3278,7 +3279,7 @@ extern "C" int tts_hip_gemv_res(tts_hip_backend_t be, int type, const void * w, 
         j.res = res;
         j.rcs = N;
     }
-    const bool q80pro = type == TTS_TYPE_Q8_0 && K % QK_K == 0 && M <= 8 && be->gemv_q80_pro;
+    const bool q80pro = tts::wtype_q80_act(type) && K % QK_K == 0 && M <= 8 && be->gemv_q80_pro;
     if (type == TTS_TYPE_Q4_K || q80pro) {
         j.pro = PRO_QUANT;
         j.tiled = (wflags & TTS_FLAG_TILED) ? 1 : 0;

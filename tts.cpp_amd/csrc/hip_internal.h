@@ -191,7 +191,7 @@ struct ActQuant {
 // optional fused epilogue (GELU table, or + residual(row n, column m) = res[m*rcs + n]).
 // EPI_SWIGLU (matrix-core Q4_K kernel only, nmat == 2: gate, up): Y[0] = silu(gate) * up, the
 // UNARY SILU and MUL of the SwiGLU MLP (Orpheus model.cpp:296-300); gate / up are never stored.
-// EPI_SILU_MUL (Q8_0 kernels): y = silu(res) * product -- the up product's epilogue reading the gate
+// EPI_SILU_MUL (Q8_0 / Q5_0 kernels): y = silu(res) * product -- the up product's epilogue reading the gate
 // product stored by the previous launch (Dia's MLP: MUL(SILU(gate x), up x)), as UNARY SILU then MUL round.
 enum { EPI_NONE = 0, EPI_GELU = 1, EPI_ADD = 2, EPI_SWIGLU = 3, EPI_SILU_MUL = 4 };
 constexpr int GEMV_MAX_MATS = 16;
@@ -411,6 +411,10 @@ struct tts_hip_backend {
     int gemv_q80_slab = 1;     // TTS_HIP_OPT_GEMV_Q80_SLAB
     int gemv_q80_rw = 0;       // TTS_HIP_OPT_GEMV_Q80_RW
     int gemm_q8_staged = 2;    // TTS_HIP_OPT_GEMM_Q8_STAGED
+    int gemv_q50_slab = 1;     // TTS_HIP_OPT_GEMV_Q50_SLAB
+    int gemv_q50_rw = 0;       // TTS_HIP_OPT_GEMV_Q50_RW
+    int gemm_q5 = 1;           // TTS_HIP_OPT_GEMM_Q5
+    int gemm_q5_staged = 2;    // TTS_HIP_OPT_GEMM_Q5_STAGED
     int64_t gemv_kr_ink = 0;   // TTS_HIP_OPT_GEMV_KR_INKERNEL (max K)
     int gemm_kr_walk = 0;      // TTS_HIP_OPT_GEMM_KR_WALK: row-tile walkers per column tile of a many-column GEMM
     int gemm_pf = 64;          // TTS_HIP_OPT_GEMM_PF: many-column Q4_K products of >= value columns on k_gemm_q4K_pf (0 = off)

@@ -1,6 +1,6 @@
-// Weight quantizers on the device: ggml's quantize_row_q4_K_ref and quantize_row_q8_0_ref
+// Weight quantizers on the device: ggml's quantize_row_q4_K_ref, quantize_row_q8_0_ref and quantize_row_q5_0_ref
 // (ggml-quants.c; restated in oracle/ggml_ref.c), so f32 weights can be turned into GGUF-compatible
-// Q4_K / Q8_0 bytes where they live (the reference's examples/quantize path, quantize_impl.cpp:82-292,
+// Q4_K / Q8_0 / Q5_0 bytes where they live (the reference's examples/quantize path, quantize_impl.cpp:82-292,
 // does this on the CPU).  Every float operation is the reference's, in source order, rounded to f32
 // (-ffp-contract=off; sqrt and division correctly rounded), so the bytes equal the CPU's.
 //
@@ -208,6 +208,35 @@ __global__ __launch_bounds__(256) void k_quantize_q8_0(const float * __restrict_
     for (int j = 0; j < 32; ++j) y[2 + j] = (uint8_t)(int8_t)roundf(__fmul_rn(xs[j], id));
 }
 
+// quantize_row_q5_0_ref: one thread per 32-value block.  max = the signed value of largest magnitude (the
+// first of equals), d = max / -16, id = d ? 1 / d : 0, q = min(31, (int8_t)(x * id + 16.5f)) (truncation);
+// the low four bits of elements j / j + 16 share qs[j], their fifth bits go to bits j / j + 16 of qh.
+__global__ __launch_bounds__(256) void k_quantize_q5_0(const float * __restrict__ x, uint8_t * __restrict__ dst, int64_t rows, int64_t K) {
+    const int64_t nbr = K / 32, nblk = rows * nbr;
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= nblk) return;
+    const float * xs = x + (b / nbr) * K + (b % nbr) * 32;
+    float amax = 0.0f, vmax = 0.0f;
+    for (int j = 0; j < 32; ++j) {
+        const float v = xs[j];
+        if (amax < fabsf(v)) amax = fabsf(v), vmax = v;
+    }
+    const float d = cr_divf(vmax, -16.f);
+    const float id = d != 0.f ? cr_divf(1.0f, d) : 0.0f;
+    uint8_t * y = dst + b * 22;
+    const uint16_t dh = q_fp32_to_fp16(d);
+    y[0] = (uint8_t)(dh & 0xFF), y[1] = (uint8_t)(dh >> 8);
+    uint32_t qh = 0;
+    for (int j = 0; j < 16; ++j) {
+        const int q0 = min(31, (int)(int8_t)__fadd_rn(__fmul_rn(xs[j], id), 16.5f));
+        const int q1 = min(31, (int)(int8_t)__fadd_rn(__fmul_rn(xs[j + 16], id), 16.5f));
+        y[6 + j] = (uint8_t)((q0 & 0x0F) | ((q1 & 0x0F) << 4));
+        qh |= (uint32_t)((q0 >> 4) & 1) << j;
+        qh |= (uint32_t)((q1 >> 4) & 1) << (j + 16);
+    }
+    y[2] = (uint8_t)qh, y[3] = (uint8_t)(qh >> 8), y[4] = (uint8_t)(qh >> 16), y[5] = (uint8_t)(qh >> 24);
+}
+
 }  // namespace
 
 }  // namespace tts
@@ -223,6 +252,10 @@ extern "C" int tts_hip_quantize(tts_hip_backend_t be, int type, const float * x,
         if (K % 32) return TTS_STATUS_BAD_ARG;
         const int64_t nblk = rows * (K / 32);
         hipLaunchKernelGGL(tts::k_quantize_q8_0, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, be->stream, x, (uint8_t *)dst, rows, K);
+    } else if (type == TTS_TYPE_Q5_0) {
+        if (K % 32) return TTS_STATUS_BAD_ARG;
+        const int64_t nblk = rows * (K / 32);
+        hipLaunchKernelGGL(tts::k_quantize_q5_0, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, be->stream, x, (uint8_t *)dst, rows, K);
     } else {
         return TTS_STATUS_UNSUPPORTED;
     }

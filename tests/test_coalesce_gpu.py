@@ -239,7 +239,9 @@ def test_weights_that_differ_are_not_shared():
 @pytest.mark.gpu
 def test_parler_mini_8_runners_coalesced_bit_identical():
     """Parler-mini Q4_K (full shapes), 8 one-prompt runners at 8 different prompt lengths on 8 backends
-    from 8 threads: tokens bit-identical to each runner decoding alone."""
+    from 8 threads: tokens bit-identical to each runner decoding alone.  (A HIP-vs-HIP comparison at full
+    shapes; the routes its launches take are compared with the CPU oracle, logits bit for bit, at small
+    shapes in tests/test_coalesce_paths_gpu.py.)"""
     cfg = ttship.parler_config(batch=1, max_ctx=256)
     n, steps = 8, 10
     prompts = [prompt(r, 12 + r, cfg.prompt_vocab) for r in range(n)]

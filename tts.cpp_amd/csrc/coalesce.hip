@@ -436,6 +436,14 @@ void run_group(Dev & d, std::vector<Req *> & g) {
     copy_options(ex, r0->be);
     // the members' queued work (their input uploads) first.  A member whose stream has drained (its
     // synchronous tensor_set uploads have, the usual case) has nothing to order behind: no fence.
+    // The skip relies on one ordering invariant: everything that writes a member's inputs or caches
+    // before its graph_compute is queued on that member's own stream (tensor_set, tensor_set_async,
+    // tensor_copy, memset and the member's earlier graphs all are; a side stream rejoins it before its
+    // graph_compute returns).  hipStreamQuery then answers for all of those writes: done (visible to
+    // the executor's launches, no fence), or not yet (the event fence below orders the step behind
+    // them -- uploads queued with tensor_set_async right before graph_compute take this branch,
+    // tests/test_coalesce_paths_gpu.py).  A write issued on any other stream, or through another
+    // backend handle, is not covered: synchronise it before the member's graph_compute.
     static const bool fence_all = getenv("TTS_CO_FENCE_ALL") != nullptr;
     for (Req * m : mem) {
         if (!fence_all) {

@@ -30,7 +30,9 @@ __device__ __forceinline__ void gemm_store(const GemvJob & j, int mat, int64_t r
     } else if (j.epi == EPI_ADD) {
         v = __fadd_rn(v, j.res[col * j.rcs + row]);
     }
-    j.Y[mat][col * j.ycs[mat] + row * j.yrs[mat]] = v;
+    // a coalesced step's member-owned targets (KV-cache rows): column col at its own offset, as gemv_put
+    float * const Y = j.Y[mat] + ((j.yoff_mats >> mat) & 1 ? j.yoff[mat * j.yoff_ld + col] : 0);
+    Y[col * j.ycs[mat] + row * j.yrs[mat]] = v;
 }
 
 // ks > 1: blockIdx.z = mat * ks + split, K range [split * kc, (split + 1) * kc), f64 partials to

@@ -2634,6 +2634,9 @@ static void launch_gemv_q4k_mc(tts_hip_backend * be, const GemvJob & j) {
             one.nmat = 1;
             one.hetero = 0;
             one.W[0] = j.W[i], one.Y[0] = j.Y[i], one.ycs[0] = j.ycs[i], one.yrs[0] = j.yrs[i];
+            // a coalesced step's per-column store offsets (gemv_put) follow their matrix to slot 0
+            one.yoff = j.yoff ? j.yoff + (int64_t)i * j.yoff_ld : nullptr;
+            one.yoff_mats = (j.yoff_mats >> i) & 1;
             one.rep_mat = i == j.rep_mat ? 0 : -1;
             one.N = j.hetero ? j.roff[i + 1] - j.roff[i] : j.N;
             one.roff[0] = 0, one.roff[1] = one.N;
@@ -2662,7 +2665,10 @@ static void launch_gemv_q4k_mc(tts_hip_backend * be, const GemvJob & j) {
             GemvJob one = j;
             one.nmat = 1;
             one.W[0] = j.W[i], one.Y[0] = j.Y[i], one.ycs[0] = j.ycs[i], one.yrs[0] = j.yrs[i];
-            one.rep_mat = i == j.rep_mat ? 0 : -1;  // the repeat-copy target follows its matrix
+            // the per-column store offsets and the repeat-copy target follow their matrix
+            one.yoff = j.yoff ? j.yoff + (int64_t)i * j.yoff_ld : nullptr;
+            one.yoff_mats = (j.yoff_mats >> i) & 1;
+            one.rep_mat = i == j.rep_mat ? 0 : -1;
             one.roff[0] = 0, one.roff[1] = j.roff[i + 1] - j.roff[i];
             launch_gemv_q4k_mc<MC>(be, one);
         }

@@ -145,6 +145,22 @@ int tts_dac_config_from_gguf(const tts_gguf * g, tts_dac_config * cfg);
 /* A DAC decoder whose weights are the file's "audio_encoder.*" tensors (F32). */
 tts_dac * tts_dac_create_from_gguf(const tts_backend_iface * be, const tts_dac_config * cfg, const tts_gguf * g);
 
+/* ---- Kokoro (kokoro_model::prep_constants / assign_weight, src/models/kokoro/model.cpp:413-930) ---- */
+/* Writes the F32 synthetic model (what tts_kokoro_create fills for cfg with weight_type F32), the input of the
+ * quantize tool: general.architecture = "kokoro", the kokoro.* keys prep_constants and the generator's
+ * *_from_file builders read, the reference's tensor names under "kokoro.", one voice pack
+ * "kokoro.voice_tensors.synthetic".  Constants post_load_assign builds (LSTM initial hidden / state, sqrt_tensor,
+ * the window and sampling constants) are not in the file.  0 on success. */
+int tts_kokoro_write_synthetic_gguf(const tts_kokoro_config * cfg, const char * path);
+/* The model fields of cfg from the keys, the widths from the tensor shapes; max_tokens, max_total, seed and the
+ * arena stay as given.  0 on success. */
+int tts_kokoro_config_from_gguf(const tts_gguf * g, tts_kokoro_config * cfg);
+/* A Kokoro runner over the file's tensors, each in the type the file gives it: F32 anywhere, F16 where the
+ * quantize tool converts to F16, Q8_0 / Q5_0 where its Kokoro rule quantizes; any other type, or a quantized
+ * tensor the rule would not quantize, fails with the tensor's name on stderr.  voice names the
+ * "kokoro.voice_tensors.<voice>" pack (NULL: the file's first); a missing voice fails.  NULL on failure. */
+tts_kokoro * tts_kokoro_create_from_gguf(const tts_backend_iface * be, const tts_kokoro_config * cfg, const tts_gguf * g, const char * voice);
+
 #ifdef __cplusplus
 }
 #endif

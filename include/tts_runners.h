@@ -336,9 +336,12 @@ typedef struct tts_kokoro_gen_config {
     int32_t max_frames;           /* generator input frames per call (arena sizing) */
     int32_t debug_no_reuse;       /* 1 = every node keeps its own arena memory (node dumps) */
     int32_t weight_type;          /* TTS_TYPE_F32 (0) or TTS_TYPE_F16 (1): the F16 GGUF's matrices / conv kernels
-                                     (examples/quantize/quantize_impl.cpp:14-18 kokoro_is_f16_compatible) */
+                                     (examples/quantize/quantize_impl.cpp:14-18 kokoro_is_f16_compatible).
+                                     TTS_TYPE_Q8_0 / TTS_TYPE_Q5_0 are accepted and leave the generator F32: the
+                                     quantize tool's Kokoro rule (:20-40) quantizes none of its tensors */
     uint64_t seed;                /* synthetic weight seed base */
     uint64_t arena_bytes;         /* compute arena (0 = sized from max_frames) */
+    int32_t f16_rest;             /* 1 = the F16-compatible tensors not quantized are F16 (`quantize -nqf`); default 0 */
 } tts_kokoro_gen_config;
 
 typedef struct tts_kokoro_gen tts_kokoro_gen;
@@ -356,6 +359,9 @@ int32_t tts_kokoro_gen_last_graph_nodes(const tts_kokoro_gen * k);
 /* Weight introspection for tests: count, then name / ne[4] / f32 values of weight i (bytes). */
 int32_t tts_kokoro_gen_n_weights(const tts_kokoro_gen * k);
 uint64_t tts_kokoro_gen_weight(tts_kokoro_gen * k, int32_t i, char * name, uint64_t name_cap, int64_t * ne, float * dst, uint64_t cap);
+/* Weight i as stored: name, ne[4], ggml type and the bytes (tts_parler_weight's contract). */
+uint64_t tts_kokoro_gen_weight_raw(tts_kokoro_gen * k, int32_t i, char * name, uint64_t name_cap, int64_t * ne, int32_t * type, void * dst,
+                                   uint64_t cap);
 /* Debug: bytes of the named node of the last graph ("sine_source", "har_spec", "up.<i>",
  * "noise_conv.<i>", "noise_res.<i>", "level.<i>", "conv_post", "after_res_gen"), copied to dst
  * when cap suffices; 0 if absent. */
@@ -372,7 +378,9 @@ tts_tensor * const * tts_kokoro_gen_graph(const tts_kokoro_gen * k, int32_t * n_
  * generator above; model.cpp:1141-1242), with the host steps between them as kokoro_runner::run /
  * set_inputs do them (model.cpp:1253-1325): read the lengths back, build the [total, n] duration
  * mask, upload.  Defaults = Kokoro-82M (ALBERT 178 x 128 -> 768, 12 heads, ffn 2048, one shared
- * layer x 12; d_model 512; decoder 1024; style 2 x 128).  Synthetic weights. */
+ * layer x 12; d_model 512; decoder 1024; style 2 x 128).  tts_kokoro_create fills deterministic synthetic
+ * weights in the storage types weight_type / f16_rest select, the ones a Kokoro GGUF file from the quantize
+ * tool holds; tts_kokoro_create_from_gguf (tts_gguf.h) takes them from such a file. */
 typedef struct tts_kokoro_config {
     tts_kokoro_gen_config gen; /* generator (gen.in_channels = last decoder block width, gen.style_dim = style half) */
     int32_t n_vocab;           /* 178 phoneme ids */
@@ -397,9 +405,16 @@ typedef struct tts_kokoro_config {
     float dur_bias;            /* synthetic duration_proj bias (-2.6: ~4 frames per token) */
     float f0_mean;             /* synthetic F0 projection bias (Hz) */
     int32_t debug_no_reuse;
-    int32_t weight_type;       /* TTS_TYPE_F32 (0) or TTS_TYPE_F16 (1), for the whole model (gen.weight_type follows it) */
+    int32_t weight_type;       /* TTS_TYPE_F32 (0) or TTS_TYPE_F16 (1), for the whole model (gen.weight_type follows it), or
+                                  TTS_TYPE_Q8_0 / TTS_TYPE_Q5_0: exactly the matrices the quantize tool's Kokoro rule
+                                  quantizes (tts_gguf_tensor_rule("kokoro", "kokoro." + name) == 1: the ALBERT matrices
+                                  except *embd and the norms, text_encoder.lstm, duration_predictor.{encode, duration_proj,
+                                  shared_lstm, duration_lstm, layers.*.lstm} weights) take that type, every other tensor
+                                  is F32.  Their rows must be multiples of 32: tts_kokoro_create returns NULL otherwise */
     uint64_t seed;
     uint64_t arena_bytes;      /* 0 = sized from max_tokens / max_total */
+    int32_t f16_rest;          /* 1 = the F16-compatible tensors weight_type did not quantize are F16, what
+                                  `quantize -nqf` writes (gen.f16_rest follows it); default 0 */
 } tts_kokoro_config;
 
 typedef struct tts_kokoro tts_kokoro;
@@ -419,8 +434,12 @@ int tts_kokoro_run(tts_kokoro * k, const int32_t * tokens, int32_t n, const floa
                    int64_t * n_samples);
 int32_t tts_kokoro_last_graph_nodes(const tts_kokoro * k, int32_t which); /* 0 = duration, 1 = main */
 int32_t tts_kokoro_n_weights(const tts_kokoro * k);
-/* Weight i (front half first, then the generator's): name, ne[4], f32 values; returns bytes. */
+/* Weight i (front half first, then the generator's): name, ne[4], f32 values (F16 widened, Q8_0 / Q5_0 by
+ * ggml's dequantize_row_*); returns bytes. */
 uint64_t tts_kokoro_weight(tts_kokoro * k, int32_t i, char * name, uint64_t name_cap, int64_t * ne, float * dst, uint64_t cap);
+/* Weight i as stored: name, ne[4], ggml type and the bytes (tts_parler_weight's contract). */
+uint64_t tts_kokoro_weight_raw(tts_kokoro * k, int32_t i, char * name, uint64_t name_cap, int64_t * ne, int32_t * type, void * dst,
+                               uint64_t cap);
 /* Debug: bytes of the named node of the last duration (which = 0) or main (1) graph. */
 uint64_t tts_kokoro_get_node(tts_kokoro * k, int32_t which, const char * name, void * dst, uint64_t cap);
 tts_tensor * const * tts_kokoro_graph(const tts_kokoro * k, int32_t which, int32_t * n_nodes);

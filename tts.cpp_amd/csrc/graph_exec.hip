@@ -992,9 +992,15 @@ struct Planner {
         const tts_tensor * mm = ab->src[0];
         if (!mm || mm->op != TTS_OP_MUL_MAT || !f32_vec(mm, Hd) || !f32_vec(ab->src[1], Hd)) return false;
         const tts_tensor * w = mm->src[0];
-        if (!w || (w->type != TTS_TYPE_F32 && w->type != TTS_TYPE_F16) || w->ne[1] != Hd || w->ne[2] * w->ne[3] != 1 ||
-            w->nb[0] != tts_type_size(w->type) || (w->nb[1] & 15) || ((uintptr_t)w->data & 15))
+        if (!w || w->ne[1] != Hd || w->ne[2] * w->ne[3] != 1 || w->nb[0] != tts_type_size(w->type)) return false;
+        if (w->type == TTS_TYPE_Q8_0 || w->type == TTS_TYPE_Q5_0) {
+            // k_lstm_step_q: whole blocks in rows of at least ne0 / 32 of them, aligned as ggml aligns them (2 bytes)
+            if (w->ne[0] % 32 || w->ne[0] > kLstmQMaxK || w->nb[1] < (size_t)(w->ne[0] / 32) * w->nb[0] || (w->nb[1] & 1) ||
+                ((uintptr_t)w->data & 1))
+                return false;
+        } else if ((w->type != TTS_TYPE_F32 && w->type != TTS_TYPE_F16) || (w->nb[1] & 15) || ((uintptr_t)w->data & 15)) {
             return false;
+        }
         const tts_tensor * pre = v->src[0];
         if (!pre || pre->type != TTS_TYPE_F32 || pre->nb[0] != 4 || pre->ne[0] != Hd || pre->ne[2] * pre->ne[3] != 1) return false;
         g = LGate{a, ap, v, ab, mm};

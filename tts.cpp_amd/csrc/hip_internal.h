@@ -137,6 +137,50 @@ __device__ __forceinline__ int octet_sum_i32(int v) {
     v += dpp_i32<DPP_HALF_MIRROR>(v);
     return v;
 }
+
+// ---- Q8_0 / Q5_0 block arithmetic shared by the GEMVs (k_gemv.hip) and the quantized LSTM step (k_fused.hip) ----
+__device__ __forceinline__ float dev_fp16_to_fp32(uint16_t h) {
+    return __half2float(__ushort_as_half(h));
+}
+// quantize_row_q8_0_ref, one element per lane, the 32 lanes of a half wave holding one block: d = amax/127,
+// id = d ? 1/d : 0, q = roundf(v*id).  Returns q; d_out is the block's d rounded to fp16 (what the dot uses).
+__device__ __forceinline__ int8_t q80_quant_elem(float v, float & d_out) {
+    float a = fabsf(v);
+#pragma unroll
+    for (int off = 16; off >= 1; off >>= 1) a = fmaxf(a, __shfl_xor(a, off));
+    const float d = cr_divf(a, 127.f);
+    const float id = d != 0.f ? cr_divf(1.f, d) : 0.f;
+    d_out = __half2float(__float2half_rn(d));
+    return (int8_t)roundf(__fmul_rn(v, id));
+}
+// Q5_0: four weights per dword: nibbles (qs & 0x0F0F0F0F, or qs >> 4 for weights 16 .. 31) give q's low four
+// bits per byte; q - 16 in two's complement is that nibble with 0xF0 on top where q's fifth bit is
+// clear.  Four bits of ~qh go to the four bytes' bit 0 by one multiply (b * 0x00204081 puts bit k at
+// 8 k, the four shifted copies never overlapping), and * 0xF0 widens each to the byte's high nibble.
+__device__ __forceinline__ uint32_t q50_himask(uint32_t nqh, int s) {  // nqh = ~qh; weights s .. s + 3
+    return ((((nqh >> s) & 0xFu) * 0x00204081u) & 0x01010101u) * 0xF0u;
+}
+// the block's 32 int8 weights: wv[i] = weights 4 i .. 4 i + 3 (i < 4: low nibbles, i >= 4: high nibbles)
+__device__ __forceinline__ void q50_unpack(uint32_t qh, const uint32_t (&qs)[4], int (&wv)[8]) {
+    const uint32_t nqh = ~qh;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        wv[i] = (int)((qs[i] & 0x0F0F0F0Fu) | q50_himask(nqh, 4 * i));
+        wv[4 + i] = (int)(((qs[i] >> 4) & 0x0F0F0F0Fu) | q50_himask(nqh, 16 + 4 * i));
+    }
+}
+// exact int32 dot of a block's 32 int8 weights with 32 int8 activations (x0 = elements 0 .. 15, x1 = 16 .. 31)
+__device__ __forceinline__ int q50_dot(const int (&wv)[8], const int4 x0, const int4 x1) {
+    int s = __builtin_amdgcn_sdot4(wv[0], x0.x, 0, false);
+    s = __builtin_amdgcn_sdot4(wv[1], x0.y, s, false);
+    s = __builtin_amdgcn_sdot4(wv[2], x0.z, s, false);
+    s = __builtin_amdgcn_sdot4(wv[3], x0.w, s, false);
+    s = __builtin_amdgcn_sdot4(wv[4], x1.x, s, false);
+    s = __builtin_amdgcn_sdot4(wv[5], x1.y, s, false);
+    s = __builtin_amdgcn_sdot4(wv[6], x1.z, s, false);
+    s = __builtin_amdgcn_sdot4(wv[7], x1.w, s, false);
+    return s;
+}
 #endif
 
 inline TD make_td(const tts_tensor * t) {
@@ -558,9 +602,11 @@ void launch_im2col(tts_hip_backend * be, const tts_tensor * node);
 // One fused LSTM recurrence step (Kokoro build_lstm_run, src/models/kokoro/model.cpp:56-86): the
 // four h-GEMVs, bias and input-projection adds, gate activations and the cell update, gate order
 // I, F, G, O (weights[1], [3], [5], [7] of the reference's cell).
+constexpr int kLstmQMaxK = 512;  // longest row of the quantized step (k_lstm_step_q, k_fused.hip)
 struct LstmStepArgs {
     const float * pre[4];   // column t of each gate's input projection (W_ih x + b_ih), Hd floats
-    const void * w[4];      // W_hh [Hd rows of K], F32 or F16
+    const void * w[4];      // W_hh [Hd rows of K]: F32 or F16 (16-byte aligned rows), Q8_0 or Q5_0 (2-byte aligned rows,
+                            // K % 32 == 0, K <= kLstmQMaxK)
     int64_t w_rs[4];        // row stride, bytes
     const float * bias[4];  // b_hh [Hd]
     const float * hprev;    // [K]

@@ -117,8 +117,111 @@ __global__ __launch_bounds__(256) void k_lstm_step(LstmStepArgs a0, LstmStepArgs
     a.h[u] = __fmul_rn(cr_tanhf(c), go);
 }
 
+// The step for Q8_0 / Q5_0 recurrent weights (WT).  ggml's MUL_MAT quantizes h_prev to Q8_0
+// (quantize_row_q8_0 per 32 elements) and folds, per gate row, the blocks in ascending order from 0.0f:
+//   sumf += (float)sumi * (d_w * d_x)      sumi the exact int32 dot, every operation rounded to f32
+// (Q5_0: (d_w * d_x) * (float)sumi with quants q - 16, the same bits); then the node chain above.
+// Nothing is reassociated, so the step equals the node chain bit for bit.
+//
+// Launch contract as k_lstm_step: wave w of workgroup b owns hidden unit u = 4b + w (Hd % 4 == 0, so
+// every wave has one), blockIdx.y selects the chain.  Division of work:
+//   1. every thread requests what it will need before anything is used: its element(s) of h_prev first
+//      (vector loads return in issue order: behind the weights the quantize would wait for them), then
+//      lane l's weight block -- lane l < 4 nb owns item (block l / 4, gate l % 4), nb = K / 32 -- then the
+//      tail's bias, projection and c_prev.  A block lies at a 2-byte aligned address: one 16-bit load and
+//      8 (Q8_0) or 5 (Q5_0) dword loads from the 4-byte aligned address at or 2 bytes after its start,
+//      funnel-shifted into place; every byte read lies inside the block.
+//   2. the workgroup quantizes h_prev into LDS, a thread per element (k_quantize_q8_0's arithmetic);
+//      one barrier.
+//   3. lane l: eight sdot4 against its block's 32 B of LDS, term = (float)sumi * (d_w * d_x).
+//   4. lanes 0-3 (gate g) fold the terms of lanes g, 4 + g, 8 + g, ... in that order: sixteen bpermutes issued
+//      together, so their latencies overlap, and nb dependent adds (those past nb masked) -- the only
+//      ordered chain.
+//   5. the tail of k_lstm_step.
+// K <= kLstmQMaxK = 512: 16 blocks, so that the 4 nb items fit the 64 lanes of the unit's wave and the
+// quantized h_prev takes 512 + 64 bytes of LDS; longer rows stay with the generic nodes.
+template <int WT>
+__global__ __launch_bounds__(256) void k_lstm_step_q(LstmStepArgs a0, LstmStepArgs a1) {
+    __shared__ __attribute__((aligned(16))) int8_t xq_s[kLstmQMaxK];
+    __shared__ float xd_s[kLstmQMaxK / QK8_0];
+    constexpr int BS = WT == TTS_TYPE_Q8_0 ? 34 : 22;  // block bytes
+    constexpr int ND = WT == TTS_TYPE_Q8_0 ? 8 : 5;    // dwords beside the 16-bit word
+    // by value: the members are then scalar loads chosen by the (uniform) chain, and a lane's gate picks among
+    // registers; through a reference each lane would first load its gate's pointers from the argument block
+    const LstmStepArgs a = blockIdx.y ? a1 : a0;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int u = blockIdx.x * 4 + (tid >> 6);
+    const int K = a.K, nb = K >> 5;
+    const float hv0 = *gptr(a.hprev + min(tid, K - 1)), hv1 = *gptr(a.hprev + min(tid + 256, K - 1));
+    const int item = min(lane, 4 * nb - 1), b = item >> 2, ig = item & 3;
+    const char * wg = (const char *)(ig == 0 ? a.w[0] : ig == 1 ? a.w[1] : ig == 2 ? a.w[2] : a.w[3]);
+    const int64_t rs = ig == 0 ? a.w_rs[0] : ig == 1 ? a.w_rs[1] : ig == 2 ? a.w_rs[2] : a.w_rs[3];
+    const char * blk = wg + (int64_t)u * rs + b * BS;
+    const bool odd = ((uintptr_t)blk & 2) != 0;  // the block starts 2 bytes before a 4-byte boundary
+    const uint32_t * dp = (const uint32_t *)(blk + (odd ? 2 : 0));
+    uint32_t dw[ND + 1];
+#pragma unroll
+    for (int k = 0; k < ND; ++k) dw[k] = *gptr(dp + k);
+    dw[ND] = *gptr((const uint16_t *)(blk + (odd ? 0 : 4 * ND)));
+    const int g = lane & 3;  // the tail: lane g evaluates gate g
+    const float bg = *gptr((g == 0 ? a.bias[0] : g == 1 ? a.bias[1] : g == 2 ? a.bias[2] : a.bias[3]) + u);
+    const float pg = *gptr((g == 0 ? a.pre[0] : g == 1 ? a.pre[1] : g == 2 ? a.pre[2] : a.pre[3]) + u);
+    const float cp = *gptr(a.cprev + u);
+    TTS_PIN_LOADS();
+    {
+        // whole 32-lane groups are in or out together (K % 32 == 0); the lanes past K quantize a copy of the
+        // last element and store nothing
+        float d0;
+        const int8_t q0 = q80_quant_elem(hv0, d0);
+        if (tid < K) xq_s[tid] = q0;
+        if ((tid & 31) == 0 && tid < K) xd_s[tid >> 5] = d0;
+        if (K > 256) {  // uniform
+            float d1;
+            const int8_t q1 = q80_quant_elem(hv1, d1);
+            if (tid + 256 < K) xq_s[tid + 256] = q1;
+            if ((tid & 31) == 0 && tid + 256 < K) xd_s[(tid + 256) >> 5] = d1;
+        }
+    }
+    __syncthreads();
+    // the block's scale and its 32 int8 weights
+    uint32_t q[ND];  // Q8_0: the quants; Q5_0: qh, qs[0 .. 3]
+#pragma unroll
+    for (int k = 0; k < ND; ++k) q[k] = odd ? dw[k] : __builtin_amdgcn_alignbit(dw[k + 1], dw[k], 16);
+    const float d_w = dev_fp16_to_fp32((uint16_t)((odd ? dw[ND] : dw[0]) & 0xFFFFu));
+    int wv[8];
+    if constexpr (WT == TTS_TYPE_Q8_0) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) wv[k] = (int)q[k];
+    } else {
+        const uint32_t qs[4] = {q[1], q[2], q[3], q[4]};
+        q50_unpack(q[0], qs, wv);
+    }
+    const int4 * xb = (const int4 *)(xq_s + b * QK8_0);
+    const int sumi = q50_dot(wv, xb[0], xb[1]);
+    const float dd = __fmul_rn(d_w, xd_s[b]);
+    const float term = WT == TTS_TYPE_Q8_0 ? __fmul_rn((float)sumi, dd) : __fmul_rn(dd, (float)sumi);
+    // all kLstmQMaxK / 32 exchanges are issued before the first add (a loop to nb would wait for each in turn)
+    float tk[kLstmQMaxK / QK8_0];
+#pragma unroll
+    for (int k = 0; k < kLstmQMaxK / QK8_0; ++k) tk[k] = __shfl(term, 4 * k + g);
+    float sum = 0.f;
+#pragma unroll
+    for (int k = 0; k < kLstmQMaxK / QK8_0; ++k) sum = k < nb ? __fadd_rn(sum, tk[k]) : sum;
+    const float t1 = __fadd_rn(sum, bg);
+    const float x = __fadd_rn(pg, t1);
+    const float gate = g == 2 ? cr_tanhf(x) : cr_divf(1.f, __fadd_rn(1.f, cr_expf(-x)));
+    const float gi = __shfl(gate, 0), gf = __shfl(gate, 1), gg = __shfl(gate, 2), go = __shfl(gate, 3);
+    if (lane != 0) return;
+    const float c = __fadd_rn(__fmul_rn(gf, cp), __fmul_rn(gi, gg));
+    a.c[u] = c;
+    a.h[u] = __fmul_rn(cr_tanhf(c), go);
+}
+
 void launch_lstm_step(tts_hip_backend * be, const LstmStepArgs & a, const LstmStepArgs * b) {
-    hipLaunchKernelGGL(k_lstm_step, dim3((unsigned)((a.Hd + 3) / 4), b ? 2u : 1u), dim3(256), 0, be->stream, a, b ? *b : a);
+    const dim3 grid((unsigned)((a.Hd + 3) / 4), b ? 2u : 1u);
+    if (a.wtype == TTS_TYPE_Q8_0) hipLaunchKernelGGL(k_lstm_step_q<TTS_TYPE_Q8_0>, grid, dim3(256), 0, be->stream, a, b ? *b : a);
+    else if (a.wtype == TTS_TYPE_Q5_0) hipLaunchKernelGGL(k_lstm_step_q<TTS_TYPE_Q5_0>, grid, dim3(256), 0, be->stream, a, b ? *b : a);
+    else hipLaunchKernelGGL(k_lstm_step, grid, dim3(256), 0, be->stream, a, b ? *b : a);
     TTS_HIP_CHECK(hipGetLastError());
 }
 

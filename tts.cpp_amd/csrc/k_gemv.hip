@@ -24,10 +24,6 @@
 
 namespace tts {
 
-__device__ __forceinline__ float dev_fp16_to_fp32(uint16_t h) {
-    return __half2float(__ushort_as_half(h));
-}
-
 __device__ __forceinline__ int dev_nearest_int(float f) {
     const float val = __fadd_rn(f, 12582912.f);
     const int i = __float_as_int(val);
@@ -124,14 +120,9 @@ __global__ __launch_bounds__(256) void k_quantize_q8_0(const float * __restrict_
     const int m = blockIdx.y;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= K) return;  // K % 32 == 0, so whole 32-blocks drop out together
-    const float v = x[m * xcs + i];
-    float a = fabsf(v);
-#pragma unroll
-    for (int off = 16; off >= 1; off >>= 1) a = fmaxf(a, __shfl_xor(a, off));
-    const float d = cr_divf(a, 127.f);
-    const float id = d != 0.f ? cr_divf(1.f, d) : 0.f;
-    qs[m * K + i] = (int8_t)roundf(__fmul_rn(v, id));
-    if ((threadIdx.x & 31) == 0) dout[m * (K / QK8_0) + i / QK8_0] = __half2float(__float2half_rn(d));
+    float d;
+    qs[m * K + i] = q80_quant_elem(x[m * xcs + i], d);
+    if ((threadIdx.x & 31) == 0) dout[m * (K / QK8_0) + i / QK8_0] = d;
 }
 
 // F16 activations: GGML_FP32_TO_FP16 (round to nearest even).
@@ -2214,34 +2205,7 @@ __global__ __launch_bounds__(256) void k_gemv_q8_0s(GemvJob j, int RW) {
 // [-16, 15] with the activation's int8.  A Q5_0 block {f16 d; u8 qh[4]; u8 qs[16]} is the Q8_0 block
 // of the same d whose quants are q - 16, and ggml_vec_dot_q8_0_q8_0 rounds the same three operations
 // in the same order, so the Q8_0 kernels' arithmetic applies once the int8 weights stand in registers.
-//
-// Four weights per dword: nibbles (qs & 0x0F0F0F0F, or qs >> 4 for weights 16 .. 31) give q's low four
-// bits per byte; q - 16 in two's complement is that nibble with 0xF0 on top where q's fifth bit is
-// clear.  Four bits of ~qh go to the four bytes' bit 0 by one multiply (b * 0x00204081 puts bit k at
-// 8 k, the four shifted copies never overlapping), and * 0xF0 widens each to the byte's high nibble.
-__device__ __forceinline__ uint32_t q50_himask(uint32_t nqh, int s) {  // nqh = ~qh; weights s .. s + 3
-    return ((((nqh >> s) & 0xFu) * 0x00204081u) & 0x01010101u) * 0xF0u;
-}
-// the block's 32 int8 weights: wv[i] = weights 4 i .. 4 i + 3 (i < 4: low nibbles, i >= 4: high nibbles)
-__device__ __forceinline__ void q50_unpack(uint32_t qh, const uint32_t (&qs)[4], int (&wv)[8]) {
-    const uint32_t nqh = ~qh;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        wv[i] = (int)((qs[i] & 0x0F0F0F0Fu) | q50_himask(nqh, 4 * i));
-        wv[4 + i] = (int)(((qs[i] >> 4) & 0x0F0F0F0Fu) | q50_himask(nqh, 16 + 4 * i));
-    }
-}
-__device__ __forceinline__ int q50_dot(const int (&wv)[8], const int4 x0, const int4 x1) {
-    int s = __builtin_amdgcn_sdot4(wv[0], x0.x, 0, false);
-    s = __builtin_amdgcn_sdot4(wv[1], x0.y, s, false);
-    s = __builtin_amdgcn_sdot4(wv[2], x0.z, s, false);
-    s = __builtin_amdgcn_sdot4(wv[3], x0.w, s, false);
-    s = __builtin_amdgcn_sdot4(wv[4], x1.x, s, false);
-    s = __builtin_amdgcn_sdot4(wv[5], x1.y, s, false);
-    s = __builtin_amdgcn_sdot4(wv[6], x1.z, s, false);
-    s = __builtin_amdgcn_sdot4(wv[7], x1.w, s, false);
-    return s;
-}
+// The unpack (q50_unpack) and the block dot (q50_dot) stand in hip_internal.h: the fused LSTM step uses them too.
 
 // The general form (K % 32 == 0, any alignment, <= 8 columns), k_gemv_q8_0's structure: a thread per
 // (row, block) computes the exact int dots for every column -> LDS, then a lane per (row, column)

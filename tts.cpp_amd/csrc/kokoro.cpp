@@ -49,6 +49,7 @@ struct tts_kokoro_gen {
     tts_kokoro_gen_config cfg;
     tts_backend_iface be;
     weight_store w;  // the weights, declaration order
+    std::string type_err;  // the first file tensor whose type the runner cannot take
     std::vector<kk_up> ups;
     std::vector<kk_res> res;  // n_ups * n_kernels
     tts_tensor *m_w = nullptr, *m_b = nullptr, *out_w = nullptr, *out_b = nullptr;
@@ -86,11 +87,14 @@ extern "C" void tts_kokoro_gen_default_config(tts_kokoro_gen_config * c) {
     c->arena_bytes = 0;
 }
 
-// gguf = false: a constant kokoro's post_load_assign builds (model.cpp:305-392), never in the file (F32)
+// gguf = false: a constant kokoro's post_load_assign builds (model.cpp:305-392), never in the file (F32).
+// The generator has no tensor the Kokoro rule quantizes: a quantized weight_type leaves it F32 (F16 with f16_rest).
 static tts_tensor * wnew(tts_kokoro_gen * k, float scale, float offset, int64_t ne0, int64_t ne1, int64_t ne2, const std::string & name,
                          bool gguf = true) {
-    const int ty = gguf && k->cfg.weight_type == TTS_TYPE_F16 && kokoro_f16_tensor(name, ne1) ? TTS_TYPE_F16 : TTS_TYPE_F32;
-    return k->w.add(ty, ne0, ne1, ne2, name, weight_fill::uniform(scale, offset), k->cfg.seed ^ k->w.index(), gguf);
+    int ty = gguf ? kokoro_tensor_type(k->cfg.weight_type, k->cfg.f16_rest, name, ne0, ne1, nullptr) : TTS_TYPE_F32;
+    if (gguf) ty = kokoro_store_type(k->w, ty, name, ne0, ne1, &k->type_err);
+    const weight_fill fill = ty == TTS_TYPE_Q8_0 || ty == TTS_TYPE_Q5_0 ? weight_fill::matrix(scale / std::sqrt(3.0f)) : weight_fill::uniform(scale, offset);
+    return k->w.add(ty, ne0, ne1, ne2, name, fill, k->cfg.seed ^ k->w.index(), gguf);
 }
 
 // conv kernel [K, IC, OC], uniform +-gain*sqrt(3/fan_in)
@@ -139,22 +143,69 @@ uint64_t kokoro_read_weight(const tts_backend_iface & be, const tts_tensor * t, 
         for (size_t i = 0; i < h.size(); ++i) dst[i] = fp16_to_fp32_host(h[i]);
         return n;
     }
+    if (t->type == TTS_TYPE_Q8_0 || t->type == TTS_TYPE_Q5_0) {
+        std::vector<uint8_t> q(tg::nbytes(t));
+        if (be.get(be.ctx, q.data(), t->data, q.size()) != 0) return 0;
+        const size_t nblk = (size_t)tg::nelements(t) / 32;
+        for (size_t b = 0; b < nblk; ++b) {
+            float * y = dst + 32 * b;
+            if (t->type == TTS_TYPE_Q8_0) {  // dequantize_row_q8_0
+                const block_q8_0 * x = (const block_q8_0 *)q.data() + b;
+                const float d = fp16_to_fp32_host(x->d);
+                for (int j = 0; j < 32; ++j) y[j] = x->qs[j] * d;
+            } else {  // dequantize_row_q5_0
+                const block_q5_0 * x = (const block_q5_0 *)q.data() + b;
+                const float d = fp16_to_fp32_host(x->d);
+                uint32_t qh;
+                memcpy(&qh, x->qh, 4);
+                for (int j = 0; j < 16; ++j) {
+                    const uint8_t xh_0 = ((qh >> (j + 0)) << 4) & 0x10;
+                    const uint8_t xh_1 = ((qh >> (j + 12))) & 0x10;
+                    y[j] = (float)(((x->qs[j] & 0x0F) | xh_0) - 16) * d;
+                    y[j + 16] = (float)(((x->qs[j] >> 4) | xh_1) - 16) * d;
+                }
+            }
+        }
+        return n;
+    }
     return be.get(be.ctx, dst, t->data, n) != 0 ? 0 : n;
 }
 }  // namespace tts
 
-extern "C" tts_kokoro_gen * tts_kokoro_gen_create(const tts_backend_iface * be, const tts_kokoro_gen_config * cfg) {
-    const auto & c = *cfg;
+static bool config_ok(const tts_kokoro_gen_config & c) {
     if (c.n_ups < 1 || c.n_ups > 4 || c.n_kernels < 1 || c.n_kernels > 4 || c.n_fft < 2 || c.hop < 1 || c.harmonic_num < 0)
-        return nullptr;
+        return false;
     // the sine source always interpolates by 300 (model.cpp:175), so the upsamplers and the iSTFT
     // hop must multiply to 300 for the harmonic branch and the main branch to line up
-    if (upsample_total(c) != kUpsample) return nullptr;
+    if (upsample_total(c) != kUpsample) return false;
     for (int i = 0; i < c.n_ups; ++i)
-        if (c.up_kernels[i] < c.up_rates[i] || (c.up_kernels[i] - c.up_rates[i]) % 2) return nullptr;
-    auto * k = new tts_kokoro_gen();
-    k->cfg = c;
-    k->be = *be;
+        if (c.up_kernels[i] < c.up_rates[i] || (c.up_kernels[i] - c.up_rates[i]) % 2) return false;
+    return true;
+}
+
+// The runner's tensor names -> assign_generator_weight's / assign_gen_resblock's (model.cpp:429-515), after
+// "kokoro.decoder.generator.": ups.<i>.{weight,bias}, noise_blocks.<i>.{conv_weight,conv_bias,resblock.<j>.*},
+// resblocks.<i>.<j>.*, m_source_{weight,bias}, conv_post_{weight,bias}.
+static std::string gen_file_name(const std::string & name) {
+    std::string n = name.compare(0, 4, "gen.") == 0 ? name.substr(4) : name;
+    auto sub = [&](const char * from, const char * to) {
+        const size_t at = n.find(from);
+        if (at != std::string::npos) n.replace(at, strlen(from), to);
+    };
+    sub(".input_conv.weight", ".conv_weight");
+    sub(".input_conv.bias", ".conv_bias");
+    sub(".res_block.", ".resblock.");
+    if (n.compare(0, 11, "res_blocks.") == 0) n = "resblocks." + n.substr(11);
+    sub("conv_post.weight", "conv_post_weight");
+    sub("conv_post.bias", "conv_post_bias");
+    return n;
+}
+
+// Every tensor, in declaration order (which defines the seeds); no backend needed.
+static void declare_weights(tts_kokoro_gen * k) {
+    const auto & c = k->cfg;
+    k->w.prefix = "kokoro.decoder.generator.";
+    k->w.file_name = gen_file_name;
     const int nbins = c.n_fft / 2 + 1;
     int ch = c.in_channels;
     for (int i = 0; i < c.n_ups; ++i) {
@@ -193,10 +244,26 @@ extern "C" tts_kokoro_gen * tts_kokoro_gen_create(const tts_backend_iface * be, 
     k->samp_scalar = wnew(k, 0.f, 0.f, 1, 0, 0, "sampling_factor_scalar", false);
     k->nker = wnew(k, 0.f, 0.f, 1, 0, 0, "n_kernels_tensor", false);
     k->one = wnew(k, 0.f, 1.0f, 1, 1, 1, "one", false);
+}
+
+tts_kokoro_gen * tts::kokoro_gen_create(const tts_backend_iface * be, const tts_kokoro_gen_config * cfg, const tts_gguf * g) {
+    if (!be || !cfg || !config_ok(*cfg)) return nullptr;
+    const auto & c = *cfg;
+    auto * k = new tts_kokoro_gen();
+    k->cfg = c;
+    k->be = *be;
+    if (g) k->w.attach(g);
+    declare_weights(k);
+    if (!k->type_err.empty()) {
+        fprintf(stderr, "%s\n", k->type_err.c_str());
+        tts_kokoro_gen_free(k);
+        return nullptr;
+    }
     if (!k->w.upload(k->be)) {
         tts_kokoro_gen_free(k);
         return nullptr;
     }
+    int ch = c.in_channels >> c.n_ups;
     // hann_window (util.cpp:132-137): sin(pi * i / n)^2 in double, stored as f32
     k->h_window.resize(c.n_fft);
     for (int i = 0; i < c.n_fft; ++i) k->h_window[i] = (float)std::pow(std::sin(M_PI * (double)i / (double)c.n_fft), 2.0);
@@ -221,6 +288,76 @@ extern "C" tts_kokoro_gen * tts_kokoro_gen_create(const tts_backend_iface * be, 
         return nullptr;
     }
     return k;
+}
+
+extern "C" tts_kokoro_gen * tts_kokoro_gen_create(const tts_backend_iface * be, const tts_kokoro_gen_config * cfg) {
+    return kokoro_gen_create(be, cfg, nullptr);
+}
+
+// The keys kokoro_generator_upsample_block, build_noise_block_from_file and build_res_block_from_file read
+// (model.cpp:246-300) and prep_constants' generator keys (:879-929), then the tensors.
+int tts::kokoro_gen_write(const tts_kokoro_gen_config * cfg, tts_gguf_writer * w) {
+    if (!cfg || !config_ok(*cfg)) return TTS_STATUS_BAD_ARG;
+    tts_kokoro_gen k;  // declarations only: no backend, no buffers
+    k.cfg = *cfg;
+    declare_weights(&k);
+    const auto & c = *cfg;
+    const std::string base = "kokoro.decoder.generator.";
+    tts_gguf_set_u32(w, (base + "up_sampling_factor").c_str(), (uint32_t)upsample_total(c));
+    tts_gguf_set_u32(w, (base + "kernels").c_str(), (uint32_t)c.n_kernels);
+    tts_gguf_set_u32(w, (base + "upsamples").c_str(), (uint32_t)c.n_ups);
+    tts_gguf_set_u32(w, (base + "padding").c_str(), 3);  // conv_post: kernel 7
+    tts_gguf_set_u32(w, (base + "n_fft").c_str(), (uint32_t)c.n_fft);
+    tts_gguf_set_u32(w, (base + "hop").c_str(), (uint32_t)c.hop);
+    auto res_keys = [&](const std::string & key, const kk_res & r) {
+        for (int j = 0; j < 3; ++j) {
+            tts_gguf_set_u32(w, (key + "." + std::to_string(j) + ".padding").c_str(), (uint32_t)r.pad[j]);
+            tts_gguf_set_u32(w, (key + "." + std::to_string(j) + ".dilation").c_str(), (uint32_t)r.dil[j]);
+        }
+    };
+    for (int i = 0; i < c.n_ups; ++i) {
+        const kk_up & u = k.ups[(size_t)i];
+        tts_gguf_set_u32(w, (base + "up_convs." + std::to_string(i) + ".stride").c_str(), (uint32_t)u.stride);
+        tts_gguf_set_u32(w, (base + "up_convs." + std::to_string(i) + ".padding").c_str(), (uint32_t)u.padding);
+        tts_gguf_set_u32(w, (base + "noise_blocks." + std::to_string(i) + ".stride").c_str(), (uint32_t)u.nstride);
+        tts_gguf_set_u32(w, (base + "noise_blocks." + std::to_string(i) + ".padding").c_str(), (uint32_t)u.npadding);
+        res_keys(base + "noise_blocks." + std::to_string(i) + ".res_block", u.nres);
+    }
+    for (size_t i = 0; i < k.res.size(); ++i) res_keys(base + "res_blocks." + std::to_string(i), k.res[i]);
+    return k.w.write(w);
+}
+
+bool tts::kokoro_gen_config_from_gguf(const tts_gguf * g, tts_kokoro_gen_config * c) {
+    const std::string base = "kokoro.decoder.generator.";
+    gguf_first_u32(g, {(base + "kernels").c_str()}, &c->n_kernels);
+    gguf_first_u32(g, {(base + "upsamples").c_str()}, &c->n_ups);
+    gguf_first_u32(g, {(base + "n_fft").c_str()}, &c->n_fft);
+    gguf_first_u32(g, {(base + "hop").c_str()}, &c->hop);
+    if (c->n_ups < 1 || c->n_ups > 4 || c->n_kernels < 1 || c->n_kernels > 4) return false;
+    bool ok = true;
+    auto dim = [&](const std::string & t, int d) {
+        const int64_t v = gguf_tensor_dim(g, base + t, d);
+        if (v < 0) {
+            fprintf(stderr, "gguf: tensor '%s' is missing\n", (base + t).c_str());
+            ok = false;
+        }
+        return (int32_t)v;
+    };
+    for (int i = 0; i < c->n_ups; ++i) {
+        const std::string si = std::to_string(i);
+        if (!gguf_first_u32(g, {(base + "up_convs." + si + ".stride").c_str()}, &c->up_rates[i])) {
+            fprintf(stderr, "gguf: key '%sup_convs.%d.stride' is missing\n", base.c_str(), i);
+            ok = false;
+        }
+        c->up_kernels[i] = dim("ups." + si + ".weight", 0);
+        c->noise_res_kernels[i] = dim("noise_blocks." + si + ".resblock.0.convs1_weight", 0);
+    }
+    for (int j = 0; j < c->n_kernels; ++j) c->res_kernels[j] = dim("resblocks." + std::to_string(j) + ".0.convs1_weight", 0);
+    for (int j = 0; j < 3; ++j) gguf_first_u32(g, {(base + "res_blocks.0." + std::to_string(j) + ".dilation").c_str()}, &c->res_dilations[j]);
+    c->in_channels = dim("ups.0.weight", 2);
+    c->style_dim = dim("resblocks.0.0.gamma1_weight", 0);
+    c->harmonic_num = dim("m_source_weight", 0) - 1;
+    return ok;
 }
 
 extern "C" void tts_kokoro_gen_free(tts_kokoro_gen * k) {
@@ -420,6 +557,13 @@ extern "C" uint64_t tts_kokoro_gen_weight(tts_kokoro_gen * k, int32_t i, char * 
     if (!t) return 0;
     tg::weight_out(k->be, t, name, name_cap, ne, nullptr, nullptr, 0);
     return kokoro_read_weight(k->be, t, dst, cap);
+}
+
+// Weight i as stored: name, ne[4], ggml type and its bytes (tts_parler_weight's contract).
+extern "C" uint64_t tts_kokoro_gen_weight_raw(tts_kokoro_gen * k, int32_t i, char * name, uint64_t name_cap, int64_t * ne, int32_t * type,
+                                              void * dst, uint64_t cap) {
+    const tts_tensor * t = k ? k->w.tensor(i) : nullptr;
+    return t ? tg::weight_out(k->be, t, name, name_cap, ne, type, dst, cap) : 0;
 }
 
 // Debug: copy the named node of the last graph to host (contiguous nodes only); returns bytes.

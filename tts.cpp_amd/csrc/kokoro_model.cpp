@@ -18,7 +18,9 @@
 // LSTMs are build_lstm / build_lstm_run (:32-86) node for node; the HIP planner fuses each
 // recurrence into one kernel per step (graph_exec.hip try_lstm).
 // Weights are deterministic synthetic tensors in Kokoro-82M shapes (no checkpoints offline),
-// named as the GGUF converter names them (py-gguf/tts_encoders/kokoro_gguf_encoder.py).
+// named as the GGUF converter names them (py-gguf/tts_encoders/kokoro_gguf_encoder.py), in the storage
+// types a file from the quantize tool holds: F32, F16, or Q8_0 / Q5_0 for the tensors its Kokoro rule
+// quantizes (kokoro_tensor_type, kokoro_gen.h).
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -68,6 +70,9 @@ struct tts_kokoro {
     tts_backend_iface be;
     tts_kokoro_gen * gen = nullptr;
     weight_store w;  // the weights, declaration order
+    std::string bad_row;  // the first tensor a quantized weight_type cannot hold (rows no multiple of 32)
+    std::string type_err;  // the first file tensor whose type the runner cannot take
+    std::string voice_name = "synthetic";  // voice_tensors.<voice_name>
     // ALBERT
     tts_tensor *tok_embd, *pos_embd, *tt_values, *in_nw, *in_nb, *embd_hidden, *embd_hidden_b;
     std::vector<kk_albert_layer> layers;
@@ -122,11 +127,17 @@ extern "C" void tts_kokoro_default_config(tts_kokoro_config * c) {
     c->seed = 0x6B0C0F0ull;
 }
 
-// gguf = false: a constant built at load time (post_load_assign), never in the file (F32)
+// gguf = false: a constant built at load time (post_load_assign), never in the file (F32).
+// A tensor the quantized weight_type applies to (kokoro_tensor_type) is filled as Parler's and Dia's quantized
+// matrices are, with the uniform rule's standard deviation; F32 / F16 fills and every seed stay as they were.
 static tts_tensor * wnew(tts_kokoro * k, float scale, float offset, int64_t ne0, int64_t ne1, int64_t ne2, const std::string & name,
                          bool gguf = true) {
-    const int ty = gguf && k->cfg.weight_type == TTS_TYPE_F16 && kokoro_f16_tensor(name, ne1) ? TTS_TYPE_F16 : TTS_TYPE_F32;
-    return k->w.add(ty, ne0, ne1, ne2, name, weight_fill::uniform(scale, offset), k->cfg.seed ^ (k->w.index() * 0x9E3779B97F4A7C15ull), gguf);
+    bool bad = false;
+    int ty = gguf ? kokoro_tensor_type(k->cfg.weight_type, k->cfg.f16_rest, name, ne0, ne1, &bad) : TTS_TYPE_F32;
+    if (gguf && k->w.gguf) bad = false, ty = kokoro_store_type(k->w, ty, name, ne0, ne1, &k->type_err);
+    if (bad && k->bad_row.empty()) k->bad_row = name + " (rows of " + std::to_string(ne0) + ")";
+    const weight_fill fill = ty == TTS_TYPE_Q8_0 || ty == TTS_TYPE_Q5_0 ? weight_fill::matrix(scale / std::sqrt(3.0f)) : weight_fill::uniform(scale, offset);
+    return k->w.add(bad ? TTS_TYPE_F32 : ty, ne0, ne1, ne2, name, fill, k->cfg.seed ^ (k->w.index() * 0x9E3779B97F4A7C15ull), gguf);
 }
 
 // Linear(in -> out) as ggml holds it: [in, out], uniform +-gain*sqrt(3/in)
@@ -151,8 +162,9 @@ static kk_lstm make_lstm(tts_kokoro * k, int in, int hd, const std::string & pre
             (dir ? r.rb : r.b)[i] = b;
         }
     }
-    r.h0 = wnew(k, 0.f, 0.f, hd, 0, 0, pre + ".0.hidden");
-    r.c0 = wnew(k, 0.f, 0.f, hd, 0, 0, pre + ".0.state");
+    // post_load_assign (model.cpp:328-352) builds the zero initial hidden and cell state: not in a file
+    r.h0 = wnew(k, 0.f, 0.f, hd, 0, 0, pre + ".0.hidden", false);
+    r.c0 = wnew(k, 0.f, 0.f, hd, 0, 0, pre + ".0.state", false);
     return r;
 }
 
@@ -181,25 +193,24 @@ static kk_ada make_ada(tts_kokoro * k, int cin, int cout, bool upsample, const s
     return a;
 }
 
-extern "C" tts_kokoro * tts_kokoro_create(const tts_backend_iface * be, const tts_kokoro_config * cfg) {
-    if (!be || !cfg) return nullptr;
-    const auto & c = *cfg;
+static std::string front_file_name(const std::string & name);
+
+static bool config_ok(const tts_kokoro_config & c) {
     if (c.hidden % c.n_heads || c.d_model % 2 || c.max_tokens < 3 || c.max_tokens > c.max_context || c.max_total < 1 || c.n_decode < 1 ||
         c.te_kernel % 2 == 0 || c.n_dur_layers < 1 || c.te_depth < 0 || c.n_voice_rows < c.max_tokens - 2 || c.max_dur < 1)
-        return nullptr;
-    auto * k = new tts_kokoro();
-    k->cfg = c;
-    k->be = *be;
-    // the generator runs inside the main graph: its own arena is unused
-    tts_kokoro_gen_config gc = c.gen;
-    gc.weight_type = c.weight_type;
-    gc.max_frames = 2 * c.max_total;
-    gc.arena_bytes = 256;
-    k->gen = tts_kokoro_gen_create(be, &gc);
-    if (!k->gen) {
-        delete k;
-        return nullptr;
+        return false;
+    if (c.weight_type != TTS_TYPE_F32 && c.weight_type != TTS_TYPE_F16 && c.weight_type != TTS_TYPE_Q8_0 && c.weight_type != TTS_TYPE_Q5_0) {
+        fprintf(stderr, "kokoro: weight_type %d is not F32, F16, Q8_0 or Q5_0\n", c.weight_type);
+        return false;
     }
+    return true;
+}
+
+// Every tensor of the front half, in declaration order (which defines the seeds); no backend needed.
+static void declare_weights(tts_kokoro * k) {
+    const auto & c = k->cfg;
+    k->w.prefix = "kokoro.";  // kokoro_model::assign_weight's names (model.cpp:413-427) follow it
+    k->w.file_name = front_file_name;
     const int S = c.gen.style_dim, D = c.d_model, H2 = c.d_model / 2;
     // ALBERT (assign_albert_weight)
     k->tok_embd = wnew(k, 1.0f, 0.f, c.embd, c.n_vocab, 0, "albert.token_embd");
@@ -282,8 +293,53 @@ extern "C" tts_kokoro * tts_kokoro_create(const tts_backend_iface * be, const tt
         k->dec.push_back(make_ada(k, c.dec_dim + 2 + c.asr_res_dim, last ? c.gen.in_channels : c.dec_dim, last,
                                   "decoder.decoder_blocks." + std::to_string(i)));
     }
-    k->voice = wnew(k, 0.5f, 0.f, 2 * S, c.n_voice_rows, 0, "voice_tensors.synthetic");
+    k->voice = wnew(k, 0.5f, 0.f, 2 * S, c.n_voice_rows, 0, "voice_tensors." + k->voice_name);
     k->sqrt2 = wnew(k, 0.f, (float)std::sqrt(2.0), 1, 0, 0, "sqrt_tensor", false);
+}
+
+// The runner's names are kokoro_model::assign_*'s except ALBERT's two layer norms: the file's "ffn_norm" is the
+// norm after attention (assign_albert_weight, model.cpp:765-770, used at :994) and its "attn_norm" the norm after
+// the FFN (:735-740, used at :1005).
+static std::string front_file_name(const std::string & name) {
+    std::string n = name;
+    size_t at;
+    if ((at = n.find(".layer_out_norm")) != std::string::npos) n.replace(at, 15, ".attn_norm");
+    else if ((at = n.find(".attn_norm")) != std::string::npos) n.replace(at, 10, ".ffn_norm");
+    return n;
+}
+
+// g NULL: synthetic weights; else every file-backed tensor from g, `voice` naming the voice pack.
+static tts_kokoro * kokoro_create(const tts_backend_iface * be, const tts_kokoro_config * cfg, const tts_gguf * g, const char * voice) {
+    if (!be || !cfg || !config_ok(*cfg)) return nullptr;
+    const auto & c = *cfg;
+    auto * k = new tts_kokoro();
+    k->cfg = c;
+    k->be = *be;
+    if (voice) k->voice_name = voice;
+    // the generator runs inside the main graph: its own arena is unused
+    tts_kokoro_gen_config gc = c.gen;
+    gc.weight_type = c.weight_type;
+    gc.f16_rest = c.f16_rest;
+    gc.max_frames = 2 * c.max_total;
+    gc.arena_bytes = 256;
+    k->gen = kokoro_gen_create(be, &gc, g);
+    if (!k->gen) {
+        delete k;
+        return nullptr;
+    }
+    if (g) k->w.attach(g);
+    declare_weights(k);
+    const int S = c.gen.style_dim, D = c.d_model, H2 = c.d_model / 2;
+    if (!k->type_err.empty()) {
+        fprintf(stderr, "%s\n", k->type_err.c_str());
+        tts_kokoro_free(k);
+        return nullptr;
+    }
+    if (!k->bad_row.empty()) {
+        fprintf(stderr, "kokoro: weight_type %d needs rows of whole 32-element blocks: %s\n", c.weight_type, k->bad_row.c_str());
+        tts_kokoro_free(k);
+        return nullptr;
+    }
     if (!k->w.upload(k->be)) {
         tts_kokoro_free(k);
         return nullptr;
@@ -306,6 +362,10 @@ extern "C" tts_kokoro * tts_kokoro_create(const tts_backend_iface * be, const tt
         return nullptr;
     }
     return k;
+}
+
+extern "C" tts_kokoro * tts_kokoro_create(const tts_backend_iface * be, const tts_kokoro_config * cfg) {
+    return kokoro_create(be, cfg, nullptr, nullptr);
 }
 
 extern "C" void tts_kokoro_free(tts_kokoro * k) {
@@ -670,10 +730,132 @@ extern "C" uint64_t tts_kokoro_weight(tts_kokoro * k, int32_t i, char * name, ui
     return kokoro_read_weight(k->be, t, dst, cap);
 }
 
+extern "C" uint64_t tts_kokoro_weight_raw(tts_kokoro * k, int32_t i, char * name, uint64_t name_cap, int64_t * ne, int32_t * type, void * dst,
+                                          uint64_t cap) {
+    if (!k || i < 0) return 0;
+    if (i >= k->w.size()) return tts_kokoro_gen_weight_raw(k->gen, i - k->w.size(), name, name_cap, ne, type, dst, cap);
+    return tg::weight_out(k->be, k->w.tensor(i), name, name_cap, ne, type, dst, cap);
+}
+
 extern "C" uint64_t tts_kokoro_get_node(tts_kokoro * k, int32_t which, const char * name, void * dst, uint64_t cap) {
     return k && name ? tg::named_node_out(k->be, (which ? k->gctx : k->dctx).nodes, name, dst, cap) : 0;
 }
 
 extern "C" tts_tensor * const * tts_kokoro_graph(const tts_kokoro * k, int32_t which, int32_t * n_nodes) {
     return tg::graph_out(k ? (which ? &k->gctx : &k->dctx) : nullptr, n_nodes);
+}
+
+// ---- GGUF (runner_from_file + kokoro_model::prep_constants / assign_weight) ----
+extern "C" int tts_kokoro_write_synthetic_gguf(const tts_kokoro_config * cfg, const char * path) {
+    if (!cfg || !path || !config_ok(*cfg)) return TTS_STATUS_BAD_ARG;
+    tts_kokoro k;  // declarations only: no backend, no buffers
+    k.cfg = *cfg;
+    k.cfg.weight_type = TTS_TYPE_F32;  // the quantize tool's input
+    k.cfg.f16_rest = 0;
+    declare_weights(&k);
+    const auto & c = k.cfg;
+    tts_gguf_writer * w = tts_gguf_writer_new();
+    tts_gguf_set_str(w, "general.architecture", "kokoro");
+    // the keys prep_constants reads (model.cpp:841-930)
+    tts_gguf_set_u32(w, "kokoro.duration_predictor.albert.context_length", (uint32_t)c.max_context);
+    tts_gguf_set_u32(w, "kokoro.tokenizer.vocab_size", (uint32_t)c.n_vocab);
+    tts_gguf_set_u32(w, "kokoro.duration_predictor.albert.hidden_size", (uint32_t)c.hidden);
+    tts_gguf_set_u32(w, "kokoro.duration_predictor.albert.attn_heads", (uint32_t)c.n_heads);
+    tts_gguf_set_u32(w, "kokoro.duration_predictor.albert.layers", (uint32_t)c.n_layers);
+    tts_gguf_set_u32(w, "kokoro.duration_predictor.albert.recurrence", (uint32_t)c.n_recurrence);
+    tts_gguf_set_u32(w, "kokoro.duration_predictor.hidden_size", (uint32_t)c.d_model);
+    tts_gguf_set_u32(w, "kokoro.duration_predictor.f0_n_blocks", 3);
+    tts_gguf_set_u32(w, "kokoro.duration_predictor.layers", (uint32_t)c.n_dur_layers);
+    tts_gguf_set_u32(w, "kokoro.text_encoder.layers", (uint32_t)c.te_depth);
+    tts_gguf_set_u32(w, "kokoro.decoder.generator.layers", (uint32_t)c.n_decode);
+    int st = k.w.write(w);
+    tts_kokoro_gen_config gc = c.gen;
+    gc.weight_type = TTS_TYPE_F32;
+    gc.f16_rest = 0;
+    if (st == TTS_STATUS_SUCCESS) st = kokoro_gen_write(&gc, w);
+    if (st == TTS_STATUS_SUCCESS) st = tts_gguf_writer_write(w, path);
+    tts_gguf_writer_free(w);
+    return st;
+}
+
+// The first "kokoro.voice_tensors.*" tensor of the file (file order), or -1.
+static int64_t first_voice(const tts_gguf * g) {
+    for (int64_t i = 0; i < tts_gguf_n_tensors(g); ++i)
+        if (strncmp(tts_gguf_tensor_name(g, i), "kokoro.voice_tensors.", 21) == 0) return i;
+    return -1;
+}
+
+extern "C" int tts_kokoro_config_from_gguf(const tts_gguf * g, tts_kokoro_config * c) {
+    if (!g || !c) return TTS_STATUS_BAD_ARG;
+    const int64_t ak = tts_gguf_find_key(g, "general.architecture");
+    if (ak < 0 || !tts_gguf_get_str(g, ak) || strcmp(tts_gguf_get_str(g, ak), "kokoro") != 0) {
+        fprintf(stderr, "gguf: not a kokoro file\n");
+        return TTS_STATUS_BAD_ARG;
+    }
+    gguf_first_u32(g, {"kokoro.duration_predictor.albert.context_length"}, &c->max_context);
+    gguf_first_u32(g, {"kokoro.tokenizer.vocab_size"}, &c->n_vocab);
+    gguf_first_u32(g, {"kokoro.duration_predictor.albert.hidden_size"}, &c->hidden);
+    gguf_first_u32(g, {"kokoro.duration_predictor.albert.attn_heads"}, &c->n_heads);
+    gguf_first_u32(g, {"kokoro.duration_predictor.albert.layers"}, &c->n_layers);
+    gguf_first_u32(g, {"kokoro.duration_predictor.albert.recurrence"}, &c->n_recurrence);
+    gguf_first_u32(g, {"kokoro.duration_predictor.hidden_size"}, &c->d_model);
+    gguf_first_u32(g, {"kokoro.duration_predictor.layers"}, &c->n_dur_layers);
+    gguf_first_u32(g, {"kokoro.text_encoder.layers"}, &c->te_depth);
+    gguf_first_u32(g, {"kokoro.decoder.generator.layers"}, &c->n_decode);
+    // widths the reference takes from the tensors themselves
+    bool ok = true;
+    auto dim = [&](const char * t, int d) {
+        const int64_t v = gguf_tensor_dim(g, t, d);
+        if (v < 0) {
+            fprintf(stderr, "gguf: tensor '%s' is missing\n", t);
+            ok = false;
+        }
+        return (int32_t)v;
+    };
+    c->embd = dim("kokoro.albert.token_embd", 0);
+    c->ffn = dim("kokoro.albert.layer.0.ffn", 1);
+    c->max_dur = dim("kokoro.duration_predictor.duration_proj", 1);
+    c->dec_dim = dim("kokoro.decoder.encoder_block.conv1_weight", 2);
+    // [1, d_model, asr] in the converter's files (squeeze_3d_2d_e0, model.cpp:593-596), [d_model, asr] in ours
+    c->asr_res_dim = dim("kokoro.decoder.asr_conv_weight", 2) > 1 ? dim("kokoro.decoder.asr_conv_weight", 2) : dim("kokoro.decoder.asr_conv_weight", 1);
+    if (c->te_depth > 0) c->te_kernel = dim("kokoro.text_encoder.layers.0.weight", 0);
+    const int64_t vi = first_voice(g);
+    if (vi < 0) {
+        fprintf(stderr, "gguf: the file holds no voice pack (kokoro.voice_tensors.*)\n");
+        return TTS_STATUS_BAD_ARG;
+    }
+    int64_t vne[4];
+    tts_gguf_tensor_ndims(g, vi, vne);
+    c->n_voice_rows = (int32_t)(vne[1] * vne[2] * vne[3]);
+    if (!kokoro_gen_config_from_gguf(g, &c->gen) || !ok) return TTS_STATUS_BAD_ARG;
+    if (c->gen.style_dim * 2 != vne[0]) {
+        fprintf(stderr, "gguf: voice rows of %lld values against a style width of %d\n", (long long)vne[0], c->gen.style_dim);
+        return TTS_STATUS_BAD_ARG;
+    }
+    // weight_type / f16_rest describe synthetic weights; a loaded tensor takes the file's type
+    const int64_t qi = tts_gguf_find_tensor(g, "kokoro.albert.layer.0.q");
+    if (qi >= 0) c->weight_type = tts_gguf_tensor_type(g, qi);
+    c->gen.weight_type = c->weight_type;
+    return TTS_STATUS_SUCCESS;
+}
+
+extern "C" tts_kokoro * tts_kokoro_create_from_gguf(const tts_backend_iface * be, const tts_kokoro_config * cfg, const tts_gguf * g,
+                                                    const char * voice) {
+    if (!be || !cfg || !g) return nullptr;
+    std::string v;
+    if (voice) {
+        v = voice;
+        if (tts_gguf_find_tensor(g, ("kokoro.voice_tensors." + v).c_str()) < 0) {
+            fprintf(stderr, "gguf: the file has no voice '%s'\n", voice);
+            return nullptr;
+        }
+    } else {
+        const int64_t vi = first_voice(g);
+        if (vi < 0) {
+            fprintf(stderr, "gguf: the file holds no voice pack (kokoro.voice_tensors.*)\n");
+            return nullptr;
+        }
+        v = tts_gguf_tensor_name(g, vi) + 21;
+    }
+    return kokoro_create(be, cfg, g, v.c_str());
 }

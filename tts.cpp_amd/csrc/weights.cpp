@@ -10,7 +10,7 @@ namespace tts {
 static size_t slot(size_t nbytes) { return (nbytes + 255) & ~(size_t)255; }
 
 int weight_store::file_type(const std::string & name, int type) const {
-    const int64_t i = gguf ? tts_gguf_find_tensor(gguf, (prefix + name).c_str()) : -1;
+    const int64_t i = gguf ? tts_gguf_find_tensor(gguf, gguf_name(name).c_str()) : -1;
     return i >= 0 ? tts_gguf_tensor_type(gguf, i) : type;
 }
 
@@ -92,7 +92,7 @@ bool weight_store::upload(const tts_backend_iface & be) {
         off += slot(tg::nbytes(s.t));
         const void * src;
         if (g && s.in_file) {
-            src = gguf_source(g, prefix + s.t->name, s.t);
+            src = gguf_source(g, gguf_name(s.t->name), s.t);
             if (!src) return false;
         } else {
             host_bytes(s, host);
@@ -110,7 +110,7 @@ int weight_store::write(tts_gguf_writer * w) const {
         host_bytes(s, host);
         int nd = 4;
         while (nd > 1 && s.t->ne[nd - 1] == 1) --nd;
-        const int st = tts_gguf_add_tensor(w, (prefix + s.t->name).c_str(), s.t->type, nd, s.t->ne, host.data(), host.size());
+        const int st = tts_gguf_add_tensor(w, gguf_name(s.t->name).c_str(), s.t->type, nd, s.t->ne, host.data(), host.size());
         if (st != TTS_STATUS_SUCCESS) return st;
     }
     return TTS_STATUS_SUCCESS;

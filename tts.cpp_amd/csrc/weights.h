@@ -41,6 +41,9 @@ struct weight_store {
     std::vector<weight_spec> specs;  // declaration order
     std::string prefix;              // GGUF name of a weight = prefix + its name
     const tts_gguf * gguf = nullptr;  // the file upload() reads (attach), else synthetic values
+    // a runner whose tensor names differ from the file's: its name -> the file's (after the prefix); null = the same
+    std::string (*file_name)(const std::string &) = nullptr;
+    std::string gguf_name(const std::string & name) const { return prefix + (file_name ? file_name(name) : name); }
 
     void attach(const tts_gguf * g) { gguf = g; }
     // Storage type of `name` in the attached file; `type` without a file or without that tensor.

@@ -256,6 +256,7 @@ class KokoroGenConfig(ctypes.Structure):
         ("weight_type", ctypes.c_int32),
         ("seed", ctypes.c_uint64),
         ("arena_bytes", ctypes.c_uint64),
+        ("f16_rest", ctypes.c_int32),
     ]
 
 
@@ -287,6 +288,7 @@ class KokoroConfig(ctypes.Structure):
         ("weight_type", ctypes.c_int32),
         ("seed", ctypes.c_uint64),
         ("arena_bytes", ctypes.c_uint64),
+        ("f16_rest", ctypes.c_int32),
     ]
 
 
@@ -461,6 +463,11 @@ def lib():
         "tts_kokoro_last_graph_nodes": (i32, [vp, i32]),
         "tts_kokoro_n_weights": (i32, [vp]),
         "tts_kokoro_weight": (u64, [vp, i32, ctypes.c_char_p, u64, ctypes.POINTER(ctypes.c_int64), vp, u64]),
+        "tts_kokoro_weight_raw": (u64, [vp, i32, ctypes.c_char_p, u64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(i32), vp, u64]),
+        "tts_kokoro_gen_weight_raw": (u64, [vp, i32, ctypes.c_char_p, u64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(i32), vp, u64]),
+        "tts_kokoro_write_synthetic_gguf": (ctypes.c_int, [ctypes.POINTER(KokoroConfig), ctypes.c_char_p]),
+        "tts_kokoro_config_from_gguf": (ctypes.c_int, [vp, ctypes.POINTER(KokoroConfig)]),
+        "tts_kokoro_create_from_gguf": (vp, [ctypes.POINTER(BackendIface), ctypes.POINTER(KokoroConfig), vp, ctypes.c_char_p]),
         "tts_kokoro_get_node": (u64, [vp, i32, ctypes.c_char_p, vp, u64]),
         "tts_kokoro_graph": (vp, [vp, i32, ctypes.POINTER(i32)]),
         "tts_kokoro_gen_default_config": (None, [ctypes.POINTER(KokoroGenConfig)]),
@@ -693,6 +700,23 @@ class _Runner:
         if self.TYPED_WEIGHTS:
             return runner_weights(n_fn, w_fn, self.ptr)
         return runner_weights(n_fn, lambda ptr, i, name, cap, ne, ty, dst, n: w_fn(ptr, i, name, cap, ne, dst, n), self.ptr)
+
+    def weights_raw(self):
+        """{name: (ggml type, ne tuple, uint8 array of the stored bytes)} through tts_<PREFIX>_weight_raw (the Kokoro
+        runners, whose tts_<PREFIX>_weight returns f32 values) or the typed tts_<PREFIX>_weight."""
+        import numpy as np
+        w_fn = self._fn("weight" if self.TYPED_WEIGHTS else "weight_raw")
+        out = {}
+        for i in range(self._fn("n_weights")(self.ptr)):
+            name = ctypes.create_string_buffer(128)
+            ne = (ctypes.c_int64 * 4)()
+            ty = ctypes.c_int32()
+            n = w_fn(self.ptr, i, name, 128, ne, ctypes.byref(ty), None, 0)
+            a = np.empty(n, dtype=np.uint8)
+            if w_fn(self.ptr, i, name, 128, ne, ctypes.byref(ty), a.ctypes.data, n) != n:
+                raise RuntimeError(f"reading weight {name.value.decode()} failed")
+            out[name.value.decode()] = (ty.value, tuple(ne), a)
+        return out
 
     def plan_stats(self, mask=None):
         """Fusion coverage of the last graph (no device needed): {item kind: count, "unfused": n}."""
@@ -1181,13 +1205,22 @@ class Kokoro(_Runner):
     PREFIX = "tts_kokoro"
     TYPED_WEIGHTS = False
 
-    def __init__(self, iface, cfg):
+    def __init__(self, iface, cfg, gguf=None, voice=None):
         self.L = lib()
         self.cfg = cfg
         self._iface = iface
-        self.ptr = self.L.tts_kokoro_create(ctypes.byref(iface), ctypes.byref(cfg))
+        if gguf is None:
+            self.ptr = self.L.tts_kokoro_create(ctypes.byref(iface), ctypes.byref(cfg))
+        else:
+            self.ptr = self.L.tts_kokoro_create_from_gguf(ctypes.byref(iface), ctypes.byref(cfg), gguf.ptr, voice.encode() if voice else None)
         if not self.ptr:
             raise RuntimeError("tts_kokoro_create failed")
+
+    @classmethod
+    def from_gguf(cls, iface, g, voice=None, **kw):
+        """A runner over the open Gguf g: the model fields from its keys and shapes (kokoro_config_from_gguf), kw =
+        max_tokens, max_total, arena_bytes ...; voice = a voice pack's name (default: the file's first)."""
+        return cls(iface, kokoro_config_from_gguf(g, **kw), gguf=g, voice=voice)
 
     def durations(self, tokens):
         """tokens (n,) int -> (hidden (n, d_model + style), lengths (n,))."""
@@ -1504,6 +1537,23 @@ def t5_config_from_gguf(g, **kw):
     for k, v in kw.items():  # caller overrides (seed, arena) win
         setattr(cfg, k, v)
     return cfg
+
+
+def kokoro_config_from_gguf(g, **kw):
+    gen = kw.pop("gen", None)
+    cfg = kokoro_config(gen=gen, **kw)
+    if lib().tts_kokoro_config_from_gguf(g.ptr, ctypes.byref(cfg)) != 0:
+        raise RuntimeError("not a usable kokoro GGUF file")
+    for k, v in kw.items():  # caller overrides (max_tokens, max_total, arena) win
+        setattr(cfg, k, v)
+    return cfg
+
+
+def write_kokoro_synthetic_gguf(path, cfg):
+    """The Kokoro runner's F32 synthetic weights for cfg as a GGUF file with the reference's names and keys."""
+    st = lib().tts_kokoro_write_synthetic_gguf(ctypes.byref(cfg), str(path).encode())
+    if st != 0:
+        raise RuntimeError(f"writing {path} failed {st}")
 
 
 def write_t5_synthetic_gguf(path, cfg):

@@ -97,7 +97,7 @@ int tts_gguf_writer_write(const tts_gguf_writer * w, const char * path); /* 0 on
 
 /* ---- quantize tool (examples/quantize/quantize_impl.cpp) ---- */
 typedef struct tts_quantize_params {
-    int32_t quantize_type;                  /* TTS_TYPE_Q4_K, TTS_TYPE_Q8_0, TTS_TYPE_Q5_0 or TTS_TYPE_F16 */
+    int32_t quantize_type;                  /* TTS_TYPE_Q4_K, TTS_TYPE_Q8_0, TTS_TYPE_Q5_0, TTS_TYPE_Q4_0 or TTS_TYPE_F16 */
     int32_t quantize_output_heads;          /* quantization_params fields, same meaning */
     int32_t quantize_text_embeddings;
     int32_t quantize_cross_attn_kv;
@@ -156,7 +156,7 @@ int tts_kokoro_write_synthetic_gguf(const tts_kokoro_config * cfg, const char * 
  * arena stay as given.  0 on success. */
 int tts_kokoro_config_from_gguf(const tts_gguf * g, tts_kokoro_config * cfg);
 /* A Kokoro runner over the file's tensors, each in the type the file gives it: F32 anywhere, F16 where the
- * quantize tool converts to F16, Q8_0 / Q5_0 where its Kokoro rule quantizes; any other type, or a quantized
+ * quantize tool converts to F16, Q8_0 / Q5_0 / Q4_0 where its Kokoro rule quantizes; any other type, or a quantized
  * tensor the rule would not quantize, fails with the tensor's name on stderr.  voice names the
  * "kokoro.voice_tensors.<voice>" pack (NULL: the file's first); a missing voice fails.  NULL on failure. */
 tts_kokoro * tts_kokoro_create_from_gguf(const tts_backend_iface * be, const tts_kokoro_config * cfg, const tts_gguf * g, const char * voice);

@@ -230,10 +230,11 @@ int tts_hip_synchronize(tts_hip_backend_t backend);
  * TTS_FLAG_REPACKED on `t`; get returns ggml's native bytes. */
 int tts_hip_weight_set(tts_hip_backend_t backend, tts_tensor * t, const void * src_host);
 int tts_hip_weight_get(tts_hip_backend_t backend, const tts_tensor * t, void * dst_host);
-/* Weight quantization on the device, ggml's quantize_row_q4_K_ref / quantize_row_q8_0_ref / quantize_row_q5_0_ref
+/* Weight quantization on the device, ggml's quantize_row_q4_K_ref / quantize_row_q8_0_ref / quantize_row_q5_0_ref /
+ * quantize_row_q4_0_ref
  * (ggml-quants.c; the reference's examples/quantize path, quantize_impl.cpp:82-292): x [rows][K] f32
  * -> dst [rows][K / blck] ggml blocks (native layout, both device pointers; K % 256 == 0 for Q4_K,
- * K % 32 == 0 for Q8_0 and Q5_0).  Bytes equal the CPU reference's (f32 operations in source order). */
+ * K % 32 == 0 for Q8_0, Q5_0 and Q4_0).  Bytes equal the CPU reference's (f32 operations in source order). */
 int tts_hip_quantize(tts_hip_backend_t backend, int type, const float * x_dev, void * dst_dev, int64_t rows, int64_t K);
 /* Host helper: (inverse = 0) ggml Q4_K blocks -> backend lane layout, (1) the reverse. */
 void tts_repack_q4_K(const void * src, void * dst, int64_t nblocks, int inverse);
@@ -365,6 +366,14 @@ enum tts_hip_option {
                                       (k_gemm_q5_0 / k_gemm_q5_0s, bit-identical); 0 = one GEMV launch per 8 columns */
     TTS_HIP_OPT_GEMM_Q5_STAGED = 48, /* many-column Q5_0 GEMM with K % 256 == 0: 2 (default) = staged kernel over 64 x 128
                                       output tiles, 1 = over 64 x 64 tiles, 0 = the direct-load kernel */
+    TTS_HIP_OPT_GEMV_Q40_SLAB = 49, /* 1 (default): Q4_0 GEMVs with K % 256 == 0 (rows of 144 K / 256 bytes) run the slab kernel
+                                      (k_gemv_q4_0s, as TTS_HIP_OPT_GEMV_Q80_SLAB); 0 = the (row, block)-per-thread kernel.
+                                      TTS_HIP_OPT_GEMV_Q80_PRO governs the prologue of all three types (the activation is Q8_0) */
+    TTS_HIP_OPT_GEMV_Q40_RW = 50,  /* slab Q4_0 GEMV rows per workgroup (0 = auto: the most that still fills every CU) */
+    TTS_HIP_OPT_GEMM_Q4_0 = 51,    /* 1 (default) = Q4_0 products of more than 8 columns run the int8 matrix-core GEMM
+                                      (k_gemm_q4_0 / k_gemm_q4_0s, bit-identical); 0 = one GEMV launch per 8 columns */
+    TTS_HIP_OPT_GEMM_Q4_0_STAGED = 52, /* many-column Q4_0 GEMM with K % 256 == 0: 2 (default) = staged kernel over 64 x 128
+                                      output tiles, 1 = over 64 x 64 tiles, 0 = the direct-load kernel */
     TTS_HIP_OPT_COALESCE = 37,    /* 1 (default): while the process-wide coalescer is on (tts_hip_coalesce_enable), this
                                      backend's graph_compute of a one-prompt decode step may join the same step of other
                                      backends on the device as one coalesced launch (tts_hip_coalesce_stats); 0 = never */
@@ -464,7 +473,7 @@ int tts_sampling_device_ok(const tts_sampling * cfg, int32_t V);
 int tts_hip_counters(tts_hip_backend_t backend, int64_t * out, int n);
 
 /* Raw kernel entry points for micro-benchmarks (device pointers, current backend stream).
- * y[M][N] = W[N][K] . x[M][K]; W is `type` (Q4_K / Q8_0 / Q5_0 / F16 / F32) row-major, N rows of K.
+ * y[M][N] = W[N][K] . x[M][K]; W is `type` (Q4_K / Q8_0 / Q5_0 / Q4_0 / F16 / F32) row-major, N rows of K.
  * Q4_K weights must already be in the backend lane layout (tts_repack_q4_K). */
 int tts_hip_gemv(tts_hip_backend_t backend, int type, const void * w, const float * x, float * y,
                  int64_t K, int64_t N, int64_t M);

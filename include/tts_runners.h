@@ -29,7 +29,7 @@ typedef struct tts_parler_config {
     int32_t n_encode;        /* 3 ("female voice" T5 tokens) */
     int32_t prompt_vocab;    /* 32128 (T5) */
     int32_t max_positions;   /* 4102 */
-    int32_t weight_type;     /* TTS_TYPE_Q4_K for config 3; Q8_0, Q5_0 (the reference's published files), F16, F32 */
+    int32_t weight_type;     /* TTS_TYPE_Q4_K for config 3; Q8_0, Q5_0, Q4_0 (what the reference's tool writes), F16, F32 */
     int32_t head_type;       /* TTS_TYPE_F32 (heads unquantized by default) */
     int32_t use_cross_attn;  /* 1 */
     int32_t batch;           /* independent prompts stepped in lockstep (1 = reference graph) */
@@ -200,7 +200,7 @@ typedef struct tts_dia_config {
     int32_t encoder_vocab_size;         /* 256 (byte tokens) */
     int32_t max_generation_size;        /* 3072 */
     int32_t max_encoder_context_length; /* 1024 */
-    int32_t weight_type;                /* TTS_TYPE_Q8_0 (default) or TTS_TYPE_Q5_0; F16 / F32 */
+    int32_t weight_type;                /* TTS_TYPE_Q8_0 (default), TTS_TYPE_Q5_0 or TTS_TYPE_Q4_0; F16 / F32 */
     int32_t head_type;                  /* TTS_TYPE_F32 */
     float cfg_scale;                    /* 3.0 */
     uint64_t seed;                      /* synthetic weight seed base (0x5EED) */
@@ -337,7 +337,7 @@ typedef struct tts_kokoro_gen_config {
     int32_t debug_no_reuse;       /* 1 = every node keeps its own arena memory (node dumps) */
     int32_t weight_type;          /* TTS_TYPE_F32 (0) or TTS_TYPE_F16 (1): the F16 GGUF's matrices / conv kernels
                                      (examples/quantize/quantize_impl.cpp:14-18 kokoro_is_f16_compatible).
-                                     TTS_TYPE_Q8_0 / TTS_TYPE_Q5_0 are accepted and leave the generator F32: the
+                                     TTS_TYPE_Q8_0 / TTS_TYPE_Q5_0 / TTS_TYPE_Q4_0 are accepted and leave the generator F32: the
                                      quantize tool's Kokoro rule (:20-40) quantizes none of its tensors */
     uint64_t seed;                /* synthetic weight seed base */
     uint64_t arena_bytes;         /* compute arena (0 = sized from max_frames) */
@@ -406,7 +406,7 @@ typedef struct tts_kokoro_config {
     float f0_mean;             /* synthetic F0 projection bias (Hz) */
     int32_t debug_no_reuse;
     int32_t weight_type;       /* TTS_TYPE_F32 (0) or TTS_TYPE_F16 (1), for the whole model (gen.weight_type follows it), or
-                                  TTS_TYPE_Q8_0 / TTS_TYPE_Q5_0: exactly the matrices the quantize tool's Kokoro rule
+                                  TTS_TYPE_Q8_0 / TTS_TYPE_Q5_0 / TTS_TYPE_Q4_0: exactly the matrices the quantize tool's Kokoro rule
                                   quantizes (tts_gguf_tensor_rule("kokoro", "kokoro." + name) == 1: the ALBERT matrices
                                   except *embd and the norms, text_encoder.lstm, duration_predictor.{encode, duration_proj,
                                   shared_lstm, duration_lstm, layers.*.lstm} weights) take that type, every other tensor
@@ -434,7 +434,7 @@ int tts_kokoro_run(tts_kokoro * k, const int32_t * tokens, int32_t n, const floa
                    int64_t * n_samples);
 int32_t tts_kokoro_last_graph_nodes(const tts_kokoro * k, int32_t which); /* 0 = duration, 1 = main */
 int32_t tts_kokoro_n_weights(const tts_kokoro * k);
-/* Weight i (front half first, then the generator's): name, ne[4], f32 values (F16 widened, Q8_0 / Q5_0 by
+/* Weight i (front half first, then the generator's): name, ne[4], f32 values (F16 widened, Q8_0 / Q5_0 / Q4_0 by
  * ggml's dequantize_row_*); returns bytes. */
 uint64_t tts_kokoro_weight(tts_kokoro * k, int32_t i, char * name, uint64_t name_cap, int64_t * ne, float * dst, uint64_t cap);
 /* Weight i as stored: name, ne[4], ggml type and the bytes (tts_parler_weight's contract). */

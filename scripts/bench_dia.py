@@ -1,7 +1,7 @@
-"""Dia-1.6B Q8_0 (or Q5_0) decode throughput on one GPU (BASELINE configs[3]): synthetic weights in the exact
+"""Dia-1.6B Q8_0 (or Q5_0 / Q4_0) decode throughput on one GPU (BASELINE configs[3]): synthetic weights in the exact
 shapes, the encoder step over a Harvard-sentence prompt, then timed CFG decoder steps (greedy heads
 fed back).  Dia produces one 9-codebook DAC frame (512 samples at 44.1 kHz) per step.
-usage: bench_dia.py [steps] [decoder_layers] [--wtype q8_0|q5_0]"""
+usage: bench_dia.py [steps] [decoder_layers] [--wtype q8_0|q5_0|q4_0]"""
 import json
 import pathlib
 import sys
@@ -21,7 +21,7 @@ def main():
         i = argv.index("--wtype")
         wname = argv[i + 1].lower()
         del argv[i:i + 2]
-    wtype = {"q8_0": ttship.Q8_0, "q5_0": ttship.Q5_0}[wname]
+    wtype = {"q8_0": ttship.Q8_0, "q5_0": ttship.Q5_0, "q4_0": ttship.Q4_0}[wname]
     steps = int(argv[1]) if len(argv) > 1 else 64
     kw = {"n_decoder_layers": int(argv[2])} if len(argv) > 2 else {}
     kw["weight_type"] = wtype

@@ -7,6 +7,10 @@ bench_gemv.py q5 [reps] [rounds] [M list] [cold]: Q5_0 beside Q8_0 at the same s
 interleaved -- per (shape, M) and round the slots Q8_0, Q5_0, Q8_0 again, `reps` launches each; one JSON
 line with the per-round averages, the medians and the Q8_0-against-Q8_0 spread (the margin a Q5_0 / Q8_0
 difference has to clear).
+
+bench_gemv.py q4 [reps] [rounds] [M list] [cold]: the same with the slots Q8_0, Q5_0, Q4_0, Q8_0 again.  Cold:
+every type's launches rotate through enough copies that 512 MiB of the smallest type's weights pass between two
+uses of one copy.
 """
 import json
 import os
@@ -98,9 +102,74 @@ def compare_q5():
     hip.close()
 
 
+def compare_q4():
+    """q4 mode: per (shape, M) and round the slots Q8_0, Q5_0, Q4_0, Q8_0 again."""
+    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 40
+    rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+    mlist = [int(v) for v in sys.argv[4].split(",")] if len(sys.argv) > 4 else [1, 2, 8, 32]
+    cold = int(sys.argv[5]) if len(sys.argv) > 5 else 1
+    hip = ttship.HipBackend(0)
+    L = ttship.lib()
+    rng = np.random.default_rng(0)
+    types = (ttship.Q8_0, ttship.Q5_0, ttship.Q4_0)
+    for K, N in Q5_SHAPES:
+        dev = {}
+        for wt in types:
+            w = quant_bytes(rng, wt, K, N)
+            # cold: as many copies of the SMALLEST (Q4_0) matrix as pass 512 MiB, the same count for every type, and
+            # a type's launches go on through its copies from slot to slot and round to round: between two uses of
+            # a copy at least 512 MiB of that type's own weights pass, twice the 256 MB last-level cache
+            ncopy = -(-(512 << 20) // (ttship.row_size(ttship.Q4_0, K) * N)) if cold else 1
+            dev[wt] = [hip.alloc(w.nbytes) for _ in range(ncopy)]
+            for d in dev[wt]:
+                hip.set(d, w)
+        at = {wt: 0 for wt in types}
+        for M in mlist:
+            x = rng.standard_normal((M, K)).astype(np.float32)
+            dx, dy = hip.alloc(x.nbytes), hip.alloc(4 * M * N)
+            hip.set(dx, x)
+
+            def slot(wt, n):
+                for _ in range(n):
+                    L.tts_hip_gemv_ex(hip.ptr, wt, dev[wt][at[wt] % len(dev[wt])], dx, dy, K, N, M, 0)
+                    at[wt] += 1
+
+            for wt in dev:
+                slot(wt, 3)
+            hip.sync()
+            hip.set_option(ttship.OPT["PROFILE_GEMV"], 1)
+            order = (("q8_0_a", ttship.Q8_0), ("q5_0", ttship.Q5_0), ("q4_0", ttship.Q4_0), ("q8_0_b", ttship.Q8_0))
+            us = {key: [] for key, _ in order}
+            for _ in range(rounds):
+                for key, wt in order:
+                    hip.gemv_stats(-1, reset=True)
+                    slot(wt, reps)
+                    ms, n, _ = hip.gemv_stats(wt, reset=True)
+                    assert n == reps, (n, reps)
+                    us[key].append(round(1000.0 * ms / n, 2))
+            hip.set_option(ttship.OPT["PROFILE_GEMV"], 0)
+            med = {k: float(np.median(v)) for k, v in us.items()}
+            q8 = 0.5 * (med["q8_0_a"] + med["q8_0_b"])
+            b4 = ttship.row_size(ttship.Q4_0, K) * N
+            print(json.dumps({"K": K, "N": N, "M": M, "cold": cold, "copies": len(dev[ttship.Q4_0]), "reps": reps, "us_per_round": us, "median_us": med,
+                              "q8_0_vs_q8_0_spread_us": round(max(abs(a - b) for a, b in zip(us["q8_0_a"], us["q8_0_b"])), 2),
+                              "q8_0_vs_q8_0_margin": round(abs(med["q8_0_a"] - med["q8_0_b"]) / q8, 3),
+                              "q4_0_over_q8_0": round(med["q4_0"] / q8, 3), "q4_0_over_q5_0": round(med["q4_0"] / med["q5_0"], 3),
+                              "q5_0_over_q8_0": round(med["q5_0"] / q8, 3),
+                              "q4_0_weight_GBps": round(b4 / (med["q4_0"] * 1e-6) / 1e9, 1)}), flush=True)
+            hip.free(dx)
+            hip.free(dy)
+        for ds in dev.values():
+            for d in ds:
+                hip.free(d)
+    hip.close()
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "q5":
         return compare_q5()
+    if len(sys.argv) > 1 and sys.argv[1] == "q4":
+        return compare_q4()
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 50
     mlist = [int(v) for v in sys.argv[2].split(",")] if len(sys.argv) > 2 else [1, 8]
     tiled = int(sys.argv[3]) if len(sys.argv) > 3 else 0  # 1: Q4_K in the tile layout (matrix-core kernel)

@@ -1,4 +1,4 @@
-"""Kokoro-82M run() by weight type: F16, Q8_0 and Q5_0 runners (synthetic weights in the real shapes) in one
+"""Kokoro-82M run() by weight type: F16, Q8_0, Q5_0 and Q4_0 runners (synthetic weights in the real shapes) in one
 process, called in turn over several rounds; and, per type, both graphs with the LSTM fusion on and off.
 
 One JSON line per type: ms per run() call (median over the rounds), audio-seconds per wall-second, the
@@ -33,7 +33,7 @@ def main():
     rng = np.random.default_rng(0)
     toks = rng.integers(1, 178, n).astype(np.int32)
     toks[0] = toks[-1] = 0
-    types = [("F16", ttship.F16), ("Q8_0", ttship.Q8_0), ("Q5_0", ttship.Q5_0)]
+    types = [("F16", ttship.F16), ("Q8_0", ttship.Q8_0), ("Q5_0", ttship.Q5_0), ("Q4_0", ttship.Q4_0)]
     runners = {name: ttship.Kokoro(be.iface(), ttship.kokoro_config(max_tokens=max(n, 16), max_total=n * 12, weight_type=wt))
                for name, wt in types}
     res = {name: {"run": [], "dur": [], "dec": [], "dur_nofuse": [], "dec_nofuse": []} for name, _ in types}

@@ -1,5 +1,5 @@
 """The fused LSTM step by weight type: one bidirectional chain at Kokoro's shape (n_in 640, hidden 256)
-through the planner, slots F16, Q8_0, Q5_0, F16 in turn, several rounds in one process.
+through the planner, slots F16, Q8_0, Q5_0, Q4_0, F16 in turn, several rounds in one process.
 
 Each slot's graph (tests/lstm_quant.py: build_lstm_run node for node) is mirrored to the device once and
 timed with device events around tts_hip_graph_compute.  A graph also holds the eight input projections and
@@ -19,6 +19,7 @@ ROOT = pathlib.Path(__file__).resolve().parents[1]
 for d in ("tts.cpp_amd", "oracle", "tests"):
     sys.path.insert(0, str(ROOT / d))
 import lstm  # noqa: E402
+import lstm_q4_0 as l4  # noqa: E402
 import lstm_quant as lq  # noqa: E402
 import nodes as nd  # noqa: E402
 import ttship  # noqa: E402
@@ -74,13 +75,16 @@ def main():
     hip = ttship.HipBackend(0)
     rng = np.random.default_rng(0)
     dirs = lstm.lstm_weights(1, n_in, hd)
-    slots = [("F16", ttship.F16), ("Q8_0", ttship.Q8_0), ("Q5_0", ttship.Q5_0), ("F16b", ttship.F16)]
+    slots = [("F16", ttship.F16), ("Q8_0", ttship.Q8_0), ("Q5_0", ttship.Q5_0), ("Q4_0", ttship.Q4_0), ("F16b", ttship.F16)]
     graphs = {}
     for name, wt in slots:
         for t in (T, Ts):
             x = (rng.standard_normal((t, n_in)) * 0.5).astype(np.float32)
             g = nd.Graph()
-            lq.lstm_cell(g, x, dirs, [wt, wt])
+            if wt == ttship.Q4_0:
+                l4.lstm_cell(g, x, dirs, "general")
+            else:
+                lq.lstm_cell(g, x, dirs, [wt, wt])
             graphs[name, t] = DeviceGraph(hip, g)
     times = {k: [] for k in graphs}
     c0 = hip.counters()
@@ -100,7 +104,8 @@ def main():
                           "graph_ms_all": [round(v, 4) for v in times[name, T]]}), flush=True)
     f16 = 0.5 * (out["F16"] + out["F16b"])
     print(json.dumps({"bench": "lstm_step_summary", "f16_us": round(f16, 3), "f16_margin": round(abs(out["F16"] - out["F16b"]) / f16, 4),
-                      "q8_0_over_f16": round(out["Q8_0"] / f16, 4), "q5_0_over_f16": round(out["Q5_0"] / f16, 4)}), flush=True)
+                      "q8_0_over_f16": round(out["Q8_0"] / f16, 4), "q5_0_over_f16": round(out["Q5_0"] / f16, 4),
+                      "q4_0_over_f16": round(out["Q4_0"] / f16, 4)}), flush=True)
     for dg in graphs.values():
         dg.close()
     hip.close()

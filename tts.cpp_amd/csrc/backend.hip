@@ -742,7 +742,7 @@ int tts_hip_supports_op(const tts_tensor * n) {
         case TTS_OP_GET_ROWS:
             return n->src[1]->type == TTS_TYPE_I32 &&
                    (n->src[0]->type == TTS_TYPE_F32 || n->src[0]->type == TTS_TYPE_F16 || n->src[0]->type == TTS_TYPE_Q4_K ||
-                    n->src[0]->type == TTS_TYPE_Q8_0 || n->src[0]->type == TTS_TYPE_Q5_0);
+                    n->src[0]->type == TTS_TYPE_Q8_0 || n->src[0]->type == TTS_TYPE_Q5_0 || n->src[0]->type == TTS_TYPE_Q4_0);
         case TTS_OP_MUL_MAT: {
             const tts_tensor * a = n->src[0];
             const tts_tensor * b = n->src[1];
@@ -751,7 +751,7 @@ int tts_hip_supports_op(const tts_tensor * n) {
             if (a->ne[0] != b->ne[0] || b->ne[2] % a->ne[2] || b->ne[3] % a->ne[3]) return 0;
             if (a->type == TTS_TYPE_F32 || a->type == TTS_TYPE_F16) return 1;
             if (a->type == TTS_TYPE_Q4_K) return a->ne[0] % 256 == 0;
-            if (a->type == TTS_TYPE_Q8_0 || a->type == TTS_TYPE_Q5_0) return a->ne[0] % 32 == 0;
+            if (a->type == TTS_TYPE_Q8_0 || a->type == TTS_TYPE_Q5_0 || a->type == TTS_TYPE_Q4_0) return a->ne[0] % 32 == 0;
             return 0;
         }
         default:
@@ -806,6 +806,16 @@ extern "C" int tts_hip_set_option(tts_hip_backend_t be, int option, int value) {
         case TTS_HIP_OPT_GEMM_Q5_STAGED:
             if (value < 0 || value > 2) return TTS_STATUS_BAD_ARG;
             be->gemm_q5_staged = value;
+            return 0;
+        case TTS_HIP_OPT_GEMV_Q40_SLAB: be->gemv_q40_slab = value != 0; return 0;
+        case TTS_HIP_OPT_GEMV_Q40_RW:
+            if (value < 0 || value > 32 || (value & (value - 1))) return TTS_STATUS_BAD_ARG;
+            be->gemv_q40_rw = value;
+            return 0;
+        case TTS_HIP_OPT_GEMM_Q4_0: be->gemm_q4_0 = value != 0; return 0;
+        case TTS_HIP_OPT_GEMM_Q4_0_STAGED:
+            if (value < 0 || value > 2) return TTS_STATUS_BAD_ARG;
+            be->gemm_q4_0_staged = value;
             return 0;
         case TTS_HIP_OPT_ATTN_KS: be->attn_ks = value; return 0;
         case TTS_HIP_OPT_GEMV_NW_MIN: be->gemv_nw_min = value; return 0;

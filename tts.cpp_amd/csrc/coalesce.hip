@@ -231,6 +231,10 @@ void copy_options(tts_hip_backend * d, const tts_hip_backend * s) {
     d->gemv_q50_rw = s->gemv_q50_rw;
     d->gemm_q5 = s->gemm_q5;
     d->gemm_q5_staged = s->gemm_q5_staged;
+    d->gemv_q40_slab = s->gemv_q40_slab;
+    d->gemv_q40_rw = s->gemv_q40_rw;
+    d->gemm_q4_0 = s->gemm_q4_0;
+    d->gemm_q4_0_staged = s->gemm_q4_0_staged;
     d->gemv_kr_ink = s->gemv_kr_ink;
     d->gemm_kr_ct2 = s->gemm_kr_ct2;
     d->gemm_kr_xcd = s->gemm_kr_xcd;

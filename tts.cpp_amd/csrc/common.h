@@ -1,6 +1,7 @@
 // Internal definitions shared by the HIP backend, the graph builder and the runners.
 // Block formats follow ggml's (Q4_K: ggml-common.h block_q4_K, 144 B / 256 weights;
-// Q8_0: block_q8_0, 34 B / 32 weights; Q5_0: block_q5_0, 22 B / 32 weights) so that weight bytes produced by TTS.cpp's loader
+// Q8_0: block_q8_0, 34 B / 32 weights; Q5_0: block_q5_0, 22 B / 32 weights;
+// Q4_0: block_q4_0, 18 B / 32 weights) so that weight bytes produced by TTS.cpp's loader
 // (/root/reference/src/models/loaders.cpp:79-88) are consumed unchanged.
 #pragma once
 
@@ -21,6 +22,7 @@ namespace tts {
 constexpr int QK_K = 256;
 constexpr int QK8_0 = 32;
 constexpr int QK5_0 = 32;
+constexpr int QK4_0 = 32;
 
 struct block_q4_K {
     uint16_t d;
@@ -45,9 +47,17 @@ struct block_q5_0 {
 };
 static_assert(sizeof(block_q5_0) == 22, "q5_0 block");
 
-// the activation type a weight type's products quantize src1 to (ggml's vec_dot_type): Q5_0 and Q8_0
-// both take Q8_0
-TTS_HD bool wtype_q80_act(int t) { return t == TTS_TYPE_Q8_0 || t == TTS_TYPE_Q5_0; }
+// weight j (j < 16) = d * ((qs[j] & 15) - 8), weight j + 16 = d * ((qs[j] >> 4) - 8).  Its dot with a Q8_0
+// activation block is ((float)sumi * d_w) * d_x (ggml_vec_dot_q4_0_q8_0), not the Q8_0 / Q5_0 association
+struct block_q4_0 {
+    uint16_t d;
+    uint8_t qs[QK4_0 / 2];
+};
+static_assert(sizeof(block_q4_0) == 18, "q4_0 block");
+
+// the activation type a weight type's products quantize src1 to (ggml's vec_dot_type): Q4_0, Q5_0 and Q8_0
+// all take Q8_0
+TTS_HD bool wtype_q80_act(int t) { return t == TTS_TYPE_Q8_0 || t == TTS_TYPE_Q5_0 || t == TTS_TYPE_Q4_0; }
 
 // Host fp16 conversion: same bit-exact algorithm as ggml_compute_fp{16,32}_to_fp{32,16}.
 inline float fp16_to_fp32_host(uint16_t h) {

@@ -624,8 +624,8 @@ static uint16_t f32_to_f16(float f) {
 
 int tts_gguf_quantize(const char * in_path, const char * out_path, const tts_quantize_params * p, tts_quantize_rows_fn fn, void * fn_ctx) {
     if (!p || (p->quantize_type != TTS_TYPE_Q4_K && p->quantize_type != TTS_TYPE_Q8_0 && p->quantize_type != TTS_TYPE_Q5_0 &&
-               p->quantize_type != TTS_TYPE_F16)) {
-        fprintf(stderr, "gguf quantize: type must be Q4_K, Q8_0, Q5_0 or F16\n");
+               p->quantize_type != TTS_TYPE_Q4_0 && p->quantize_type != TTS_TYPE_F16)) {
+        fprintf(stderr, "gguf quantize: type must be Q4_K, Q8_0, Q5_0, Q4_0 or F16\n");
         return TTS_STATUS_BAD_ARG;
     }
     tts_gguf * g = tts_gguf_open(in_path);

@@ -114,7 +114,8 @@ bool is_gemv(const tts_tensor * n) {
     switch (a->type) {
         case TTS_TYPE_Q4_K: return a->ne[0] % 256 == 0;
         case TTS_TYPE_Q8_0:
-        case TTS_TYPE_Q5_0: return a->ne[0] % 32 == 0;
+        case TTS_TYPE_Q5_0:
+        case TTS_TYPE_Q4_0: return a->ne[0] % 32 == 0;
         case TTS_TYPE_F32:
         case TTS_TYPE_F16: return a->ne[0] % 4 == 0 && (b->nb[1] % 16) == 0 && ((uintptr_t)b->data % 16) == 0;
         default: return false;
@@ -993,7 +994,7 @@ struct Planner {
         if (!mm || mm->op != TTS_OP_MUL_MAT || !f32_vec(mm, Hd) || !f32_vec(ab->src[1], Hd)) return false;
         const tts_tensor * w = mm->src[0];
         if (!w || w->ne[1] != Hd || w->ne[2] * w->ne[3] != 1 || w->nb[0] != tts_type_size(w->type)) return false;
-        if (w->type == TTS_TYPE_Q8_0 || w->type == TTS_TYPE_Q5_0) {
+        if (wtype_q80_act(w->type)) {
             // k_lstm_step_q: whole blocks in rows of at least ne0 / 32 of them, aligned as ggml aligns them (2 bytes)
             if (w->ne[0] % 32 || w->ne[0] > kLstmQMaxK || w->nb[1] < (size_t)(w->ne[0] / 32) * w->nb[0] || (w->nb[1] & 1) ||
                 ((uintptr_t)w->data & 1))
@@ -1636,7 +1637,7 @@ struct Planner {
         auto leaf_ok = [&](const tts_tensor * g) {
             if (g->op != TTS_OP_GET_ROWS || sole_consumer(g) != a || g->type != TTS_TYPE_F32) return false;
             const tts_tensor *tab = g->src[0], *idx = g->src[1];
-            if (tab->type != TTS_TYPE_F32 && tab->type != TTS_TYPE_F16 && tab->type != TTS_TYPE_Q8_0 && tab->type != TTS_TYPE_Q5_0 && tab->type != TTS_TYPE_Q4_K) return false;
+            if (tab->type != TTS_TYPE_F32 && tab->type != TTS_TYPE_F16 && tab->type != TTS_TYPE_Q8_0 && tab->type != TTS_TYPE_Q5_0 && tab->type != TTS_TYPE_Q4_0 && tab->type != TTS_TYPE_Q4_K) return false;
             if (idx->type != TTS_TYPE_I32 || idx->ne[1] * idx->ne[2] * idx->ne[3] != 1 || (idx->nb[0] % 4)) return false;
             if (tab->ne[0] != root->ne[0] || g->ne[0] != root->ne[0] || tab->ne[2] * tab->ne[3] != 1) return false;
             const int64_t rows = g->ne[1] * g->ne[2] * g->ne[3], M = root->ne[1] * root->ne[2] * root->ne[3];
@@ -2123,7 +2124,7 @@ static int prepare_act(tts_hip_backend * be, int wtype, const float * x, int64_t
         out.vtype = TTS_TYPE_F32;
         return 0;
     }
-    const int vt = wtype == TTS_TYPE_Q4_K ? TTS_TYPE_Q8_K : wtype == TTS_TYPE_Q5_0 ? TTS_TYPE_Q8_0 : wtype;  // vec_dot_type
+    const int vt = wtype == TTS_TYPE_Q4_K ? TTS_TYPE_Q8_K : wtype_q80_act(wtype) ? TTS_TYPE_Q8_0 : wtype;  // vec_dot_type
     const bool hit = aq.src == x && aq.K == K && aq.M == M && aq.vtype == vt && aq.graph_epoch == be->graph_epoch;
     if (!hit) {
         if (!ensure_scratch(be, act_quant_bytes(wtype, K, M))) return TTS_STATUS_ALLOC_FAILED;
@@ -3328,7 +3329,7 @@ extern "C" int tts_hip_gemv_res(tts_hip_backend_t be, int type, const void * w, 
     if ((wflags & TTS_FLAG_TILED) && (type != TTS_TYPE_Q4_K || N % 4)) return TTS_STATUS_BAD_ARG;
     if (type == TTS_TYPE_Q4_K && K % 256) return TTS_STATUS_BAD_ARG;
     if (tts::wtype_q80_act(type) && K % 32) return TTS_STATUS_BAD_ARG;
-    if (type != TTS_TYPE_Q4_K && type != TTS_TYPE_Q8_0 && type != TTS_TYPE_Q5_0 && type != TTS_TYPE_F16 && type != TTS_TYPE_F32) return TTS_STATUS_UNSUPPORTED;
+    if (type != TTS_TYPE_Q4_K && type != TTS_TYPE_Q8_0 && type != TTS_TYPE_Q5_0 && type != TTS_TYPE_Q4_0 && type != TTS_TYPE_F16 && type != TTS_TYPE_F32) return TTS_STATUS_UNSUPPORTED;
     if ((type == TTS_TYPE_F32 || type == TTS_TYPE_F16) && K % 4) return TTS_STATUS_BAD_ARG;
     hipSetDevice(be->device);
     GemvJob j;

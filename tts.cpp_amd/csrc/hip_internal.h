@@ -138,7 +138,7 @@ __device__ __forceinline__ int octet_sum_i32(int v) {
     return v;
 }
 
-// ---- Q8_0 / Q5_0 block arithmetic shared by the GEMVs (k_gemv.hip) and the quantized LSTM step (k_fused.hip) ----
+// ---- Q8_0 / Q5_0 / Q4_0 block arithmetic shared by the GEMVs (k_gemv.hip) and the quantized LSTM step (k_fused.hip) ----
 __device__ __forceinline__ float dev_fp16_to_fp32(uint16_t h) {
     return __half2float(__ushort_as_half(h));
 }
@@ -168,6 +168,26 @@ __device__ __forceinline__ void q50_unpack(uint32_t qh, const uint32_t (&qs)[4],
         wv[i] = (int)((qs[i] & 0x0F0F0F0Fu) | q50_himask(nqh, 4 * i));
         wv[4 + i] = (int)(((qs[i] >> 4) & 0x0F0F0F0Fu) | q50_himask(nqh, 16 + 4 * i));
     }
+}
+// Q4_0: four weights per dword: a byte's nibble n in 0 .. 15 becomes the int8 n - 8 in four operations on the
+// dword (five for the high nibbles' shift): t = n ^ 8 is n - 8 for n >= 8 and n + 8 (bit 3 set) for n < 8, where
+// n - 8 is t with 0xF0 on top; (t & 0x08) * 0x1E = 0xF0 stays inside its byte.
+__device__ __forceinline__ uint32_t q40_s8(uint32_t nib) {  // nib: four bytes 0 .. 15
+    const uint32_t t = nib ^ 0x08080808u;
+    return t | ((t & 0x08080808u) * 0x1Eu);
+}
+// the block's 32 int8 weights q - 8: wv[i] = weights 4 i .. 4 i + 3 (i < 4: low nibbles, i >= 4: high nibbles)
+__device__ __forceinline__ void q40_unpack(const uint32_t (&qs)[4], int (&wv)[8]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        wv[i] = (int)q40_s8(qs[i] & 0x0F0F0F0Fu);
+        wv[4 + i] = (int)q40_s8((qs[i] >> 4) & 0x0F0F0F0Fu);
+    }
+}
+// ggml_vec_dot_q4_0_q8_0's term: ((float)sumi * d_w) * d_x, each product rounded -- not the Q8_0 / Q5_0 kernels'
+// sumi * (d_w * d_x), which differs in the last bit for about one term in ten
+__device__ __forceinline__ float q40_term(int sumi, float dw, float dx) {
+    return __fmul_rn(__fmul_rn((float)sumi, dw), dx);
 }
 // exact int32 dot of a block's 32 int8 weights with 32 int8 activations (x0 = elements 0 .. 15, x1 = 16 .. 31)
 __device__ __forceinline__ int q50_dot(const int (&wv)[8], const int4 x0, const int4 x1) {
@@ -459,6 +479,10 @@ struct tts_hip_backend {
     int gemv_q50_rw = 0;       // TTS_HIP_OPT_GEMV_Q50_RW
     int gemm_q5 = 1;           // TTS_HIP_OPT_GEMM_Q5
     int gemm_q5_staged = 2;    // TTS_HIP_OPT_GEMM_Q5_STAGED
+    int gemv_q40_slab = 1;     // TTS_HIP_OPT_GEMV_Q40_SLAB
+    int gemv_q40_rw = 0;       // TTS_HIP_OPT_GEMV_Q40_RW
+    int gemm_q4_0 = 1;         // TTS_HIP_OPT_GEMM_Q4_0
+    int gemm_q4_0_staged = 2;  // TTS_HIP_OPT_GEMM_Q4_0_STAGED
     int64_t gemv_kr_ink = 0;   // TTS_HIP_OPT_GEMV_KR_INKERNEL (max K)
     int gemm_kr_walk = 0;      // TTS_HIP_OPT_GEMM_KR_WALK: row-tile walkers per column tile of a many-column GEMM
     int gemm_pf = 64;          // TTS_HIP_OPT_GEMM_PF: many-column Q4_K products of >= value columns on k_gemm_q4K_pf (0 = off)
@@ -605,7 +629,7 @@ void launch_im2col(tts_hip_backend * be, const tts_tensor * node);
 constexpr int kLstmQMaxK = 512;  // longest row of the quantized step (k_lstm_step_q, k_fused.hip)
 struct LstmStepArgs {
     const float * pre[4];   // column t of each gate's input projection (W_ih x + b_ih), Hd floats
-    const void * w[4];      // W_hh [Hd rows of K]: F32 or F16 (16-byte aligned rows), Q8_0 or Q5_0 (2-byte aligned rows,
+    const void * w[4];      // W_hh [Hd rows of K]: F32 or F16 (16-byte aligned rows), Q8_0, Q5_0 or Q4_0 (2-byte aligned rows,
                             // K % 32 == 0, K <= kLstmQMaxK)
     int64_t w_rs[4];        // row stride, bytes
     const float * bias[4];  // b_hh [Hd]

@@ -117,10 +117,11 @@ __global__ __launch_bounds__(256) void k_lstm_step(LstmStepArgs a0, LstmStepArgs
     a.h[u] = __fmul_rn(cr_tanhf(c), go);
 }
 
-// The step for Q8_0 / Q5_0 recurrent weights (WT).  ggml's MUL_MAT quantizes h_prev to Q8_0
+// The step for Q8_0 / Q5_0 / Q4_0 recurrent weights (WT).  ggml's MUL_MAT quantizes h_prev to Q8_0
 // (quantize_row_q8_0 per 32 elements) and folds, per gate row, the blocks in ascending order from 0.0f:
 //   sumf += (float)sumi * (d_w * d_x)      sumi the exact int32 dot, every operation rounded to f32
-// (Q5_0: (d_w * d_x) * (float)sumi with quants q - 16, the same bits); then the node chain above.
+// (Q5_0: (d_w * d_x) * (float)sumi with quants q - 16, the same bits; Q4_0: ((float)sumi * d_w) * d_x with quants
+// q - 8, ggml_vec_dot_q4_0_q8_0's own association, other bits); then the node chain above.
 // Nothing is reassociated, so the step equals the node chain bit for bit.
 //
 // Launch contract as k_lstm_step: wave w of workgroup b owns hidden unit u = 4b + w (Hd % 4 == 0, so
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(256) void k_lstm_step(LstmStepArgs a0, LstmStepArgs
 //      (vector loads return in issue order: behind the weights the quantize would wait for them), then
 //      lane l's weight block -- lane l < 4 nb owns item (block l / 4, gate l % 4), nb = K / 32 -- then the
 //      tail's bias, projection and c_prev.  A block lies at a 2-byte aligned address: one 16-bit load and
-//      8 (Q8_0) or 5 (Q5_0) dword loads from the 4-byte aligned address at or 2 bytes after its start,
+//      8 (Q8_0), 5 (Q5_0) or 4 (Q4_0) dword loads from the 4-byte aligned address at or 2 bytes after its start,
 //      funnel-shifted into place; every byte read lies inside the block.
 //   2. the workgroup quantizes h_prev into LDS, a thread per element (k_quantize_q8_0's arithmetic);
 //      one barrier.
@@ -144,8 +145,8 @@ template <int WT>
 __global__ __launch_bounds__(256) void k_lstm_step_q(LstmStepArgs a0, LstmStepArgs a1) {
     __shared__ __attribute__((aligned(16))) int8_t xq_s[kLstmQMaxK];
     __shared__ float xd_s[kLstmQMaxK / QK8_0];
-    constexpr int BS = WT == TTS_TYPE_Q8_0 ? 34 : 22;  // block bytes
-    constexpr int ND = WT == TTS_TYPE_Q8_0 ? 8 : 5;    // dwords beside the 16-bit word
+    constexpr int BS = WT == TTS_TYPE_Q8_0 ? 34 : WT == TTS_TYPE_Q5_0 ? 22 : 18;  // block bytes
+    constexpr int ND = WT == TTS_TYPE_Q8_0 ? 8 : WT == TTS_TYPE_Q5_0 ? 5 : 4;     // dwords beside the 16-bit word
     // by value: the members are then scalar loads chosen by the (uniform) chain, and a lane's gate picks among
     // registers; through a reference each lane would first load its gate's pointers from the argument block
     const LstmStepArgs a = blockIdx.y ? a1 : a0;
@@ -184,7 +185,7 @@ __global__ __launch_bounds__(256) void k_lstm_step_q(LstmStepArgs a0, LstmStepAr
     }
     __syncthreads();
     // the block's scale and its 32 int8 weights
-    uint32_t q[ND];  // Q8_0: the quants; Q5_0: qh, qs[0 .. 3]
+    uint32_t q[ND];  // Q8_0: the quants; Q5_0: qh, qs[0 .. 3]; Q4_0: qs[0 .. 3]
 #pragma unroll
     for (int k = 0; k < ND; ++k) q[k] = odd ? dw[k] : __builtin_amdgcn_alignbit(dw[k + 1], dw[k], 16);
     const float d_w = dev_fp16_to_fp32((uint16_t)((odd ? dw[ND] : dw[0]) & 0xFFFFu));
@@ -192,14 +193,22 @@ __global__ __launch_bounds__(256) void k_lstm_step_q(LstmStepArgs a0, LstmStepAr
     if constexpr (WT == TTS_TYPE_Q8_0) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) wv[k] = (int)q[k];
-    } else {
+    } else if constexpr (WT == TTS_TYPE_Q5_0) {
         const uint32_t qs[4] = {q[1], q[2], q[3], q[4]};
         q50_unpack(q[0], qs, wv);
+    } else {
+        const uint32_t qs[4] = {q[0], q[1], q[2], q[3]};
+        q40_unpack(qs, wv);
     }
     const int4 * xb = (const int4 *)(xq_s + b * QK8_0);
     const int sumi = q50_dot(wv, xb[0], xb[1]);
-    const float dd = __fmul_rn(d_w, xd_s[b]);
-    const float term = WT == TTS_TYPE_Q8_0 ? __fmul_rn((float)sumi, dd) : __fmul_rn(dd, (float)sumi);
+    float term;
+    if constexpr (WT == TTS_TYPE_Q4_0) {
+        term = q40_term(sumi, d_w, xd_s[b]);
+    } else {
+        const float dd = __fmul_rn(d_w, xd_s[b]);
+        term = WT == TTS_TYPE_Q8_0 ? __fmul_rn((float)sumi, dd) : __fmul_rn(dd, (float)sumi);
+    }
     // all kLstmQMaxK / 32 exchanges are issued before the first add (a loop to nb would wait for each in turn)
     float tk[kLstmQMaxK / QK8_0];
 #pragma unroll
@@ -221,6 +230,7 @@ void launch_lstm_step(tts_hip_backend * be, const LstmStepArgs & a, const LstmSt
     const dim3 grid((unsigned)((a.Hd + 3) / 4), b ? 2u : 1u);
     if (a.wtype == TTS_TYPE_Q8_0) hipLaunchKernelGGL(k_lstm_step_q<TTS_TYPE_Q8_0>, grid, dim3(256), 0, be->stream, a, b ? *b : a);
     else if (a.wtype == TTS_TYPE_Q5_0) hipLaunchKernelGGL(k_lstm_step_q<TTS_TYPE_Q5_0>, grid, dim3(256), 0, be->stream, a, b ? *b : a);
+    else if (a.wtype == TTS_TYPE_Q4_0) hipLaunchKernelGGL(k_lstm_step_q<TTS_TYPE_Q4_0>, grid, dim3(256), 0, be->stream, a, b ? *b : a);
     else hipLaunchKernelGGL(k_lstm_step, grid, dim3(256), 0, be->stream, a, b ? *b : a);
     TTS_HIP_CHECK(hipGetLastError());
 }

@@ -1,10 +1,10 @@
-// Quantized decode GEMV for gfx950: y = W x with W in Q4_K / Q8_0 / Q5_0 / F16 / F32, M <= 8 columns.
+// Quantized decode GEMV for gfx950: y = W x with W in Q4_K / Q8_0 / Q5_0 / Q4_0 / F16 / F32, M <= 8 columns.
 //
 // Replaces GGML_OP_MUL_MAT at every decode site (Parler model.cpp:544-546,571,583,594,601,603;
 // Dia model.cpp:535-537,...; Orpheus model.cpp:254-256,...).
 //
 // Numerics are ggml-cpu's generic scalar paths, bit for bit: the activation column is quantized to
-// the weight type's vec_dot_type (Q8_K for Q4_K, Q8_0 for Q8_0 and Q5_0, F16 for F16) with the exact
+// the weight type's vec_dot_type (Q8_K for Q4_K, Q8_0 for Q8_0, Q5_0 and Q4_0, F16 for F16) with the exact
 // quantize_row_*_ref arithmetic, the per-block integer dot products are exact (v_dot4_i32_i8), and
 // the f32 combination follows vec_dot_*'s order exactly.  F32/F16 dots take f32 products and
 // accumulate them in f64, as ggml_vec_dot_f32/f16 do (tests/test_gemv_gpu.py: bit-exact).
@@ -2370,6 +2370,174 @@ __global__ __launch_bounds__(256) void k_gemv_q5_0s(GemvJob j, int RW) {
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Q4_0 x Q8_0 (ggml_vec_dot_q4_0_q8_0, generic order): per (row, column), blocks ascending,
+// sumf += ((float)sumi * d_w) * d_x, sumi the exact int32 dot of the block's 32 weights q - 8 in [-8, 7] with
+// the activation's int8.  The association differs from Q8_0's and Q5_0's sumi * (d_w * d_x), so these kernels
+// keep d_w and d_x apart until the term (q40_term); everything else is the Q5_0 kernels' structure with an
+// 18-B block {f16 d; u8 qs[16]} and a shorter unpack (q40_unpack, hip_internal.h).
+
+// The general form (K % 32 == 0, any alignment, <= 8 columns): a thread per (row, block) computes the term of
+// every column -> LDS, then a lane per (row, column) adds its blocks' terms in order.  Native blocks are 18 B
+// at a 2-B aligned address: nine 16-bit loads.  PRO as k_gemv_q8_0 (the activation is the same Q8_0).  The LDS
+// layout is k_gemv_q8_0's (q80_lds); the terms take its f32 array, the int array stays unused.
+template <int MC, int PRO = 0>
+__global__ __launch_bounds__(256) void k_gemv_q4_0(GemvJob j, int RW) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int nb = (int)(j.K / QK4_0);
+    const int mat = blockIdx.y;
+    const uint8_t * __restrict__ W = j.W[mat];
+    const int64_t row0 = (int64_t)blockIdx.x * RW;
+    const int rows = (int)((j.N - row0) < RW ? (j.N - row0) : RW);
+    const int M = j.M;
+    int8_t * xq_s = (int8_t *)smem;
+    float * xd_s = (float *)(smem + al16((size_t)MC * j.K + (PRO ? QK_K : 0)));  // + the prologue's trash slot
+    int * s_s = (int *)((char *)xd_s + al16(sizeof(float) * (MC * nb + (PRO ? QK_K / QK8_0 : 0))));
+    float * f_s = (float *)((char *)s_s + al16(sizeof(int) * (size_t)RW * nb * MC));
+    const int npairs = rows * nb;
+    // this thread's first (row, block): its 18 bytes in registers before the prologue (clamped, unconditional)
+    uint16_t h0[9];
+    {
+        const int p = min((int)threadIdx.x, npairs - 1);
+        const int r = p / nb, b = p % nb;
+        const uint16_t * bp = (const uint16_t *)(W + (row0 + r) * j.w_row_bytes + (int64_t)b * 18);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) h0[k] = *gptr(bp + k);
+    }
+    TTS_PIN_LOADS();
+    if constexpr (PRO != 0) {
+        q4k_prologue<PRO, 16, false, NoMid, true>(j, (int)(j.K / QK_K), xq_s, xd_s, nullptr);
+    } else {
+        const int4 * src = (const int4 *)j.aq.qs;
+        int4 * dst = (int4 *)xq_s;
+        const int n16 = (int)((int64_t)M * j.K / 16);
+        for (int i = threadIdx.x; i < n16; i += 256) dst[i] = src[i];
+        for (int i = threadIdx.x; i < M * nb; i += 256) xd_s[i] = j.aq.d[i];
+    }
+    __syncthreads();
+    for (int p = threadIdx.x; p < npairs; p += 256) {
+        const int r = p / nb, b = p % nb;
+        uint16_t h[9];
+        if (p == (int)threadIdx.x) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) h[k] = h0[k];
+        } else {
+            const uint16_t * bp = (const uint16_t *)(W + (row0 + r) * j.w_row_bytes + (int64_t)b * 18);
+#pragma unroll
+            for (int k = 0; k < 9; ++k) h[k] = bp[k];
+        }
+        const float dw = dev_fp16_to_fp32(h[0]);
+        uint32_t qs[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) qs[k] = (uint32_t)h[1 + 2 * k] | ((uint32_t)h[2 + 2 * k] << 16);
+        int wv[8];
+        q40_unpack(qs, wv);
+#pragma unroll
+        for (int m = 0; m < MC; ++m) {
+            if (m >= M) break;
+            const int4 * xb = (const int4 *)(xq_s + (m * nb + b) * QK8_0);
+            f_s[(r * MC + m) * nb + b] = q40_term(q50_dot(wv, xb[0], xb[1]), dw, xd_s[m * nb + b]);
+        }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < rows * MC; t += 256) {
+        const int r = t / MC, m = t % MC;
+        if (m >= M) continue;
+        float a = 0.f;
+        const int o = (r * MC + m) * nb;
+        for (int b = 0; b < nb; ++b) a = __fadd_rn(a, f_s[o + b]);
+        gemv_store<MC>(j, mat, row0 + r, m, a);
+    }
+}
+
+// The slab form (K % 256 == 0, 16-B aligned weights, <= 8 columns), k_gemv_q5_0s's structure: rows are
+// 144 K / 256 bytes (a multiple of 16), the workgroup's RW rows come whole by LDS-DMA, then from LDS
+//   terms: a thread per (row, block pair) -- the pair (2k, 2k+1) spans 36 B at a 4-B aligned offset (9
+//          dwords: d0 | qs0 .., .. qs0 | d1, qs1 x 4; block 2k's qs are the funnel-shifted dwords; the odd
+//          dword stride keeps a wave's reads on distinct banks);
+//   chain: a thread per (row, column) adds the nb terms in block order.
+// LDS: slab al1K(RW*row_bytes) | xq al1K(MC*K + 256) | xd al1K(4*(MC*nb + 8)) | terms 4*RW*MC*nb --
+// 18/34 of the Q8_0 slab, the rest equal.
+static size_t q40s_lds(int MC, int64_t K, int RW) {
+    const int64_t nb = K / QK4_0, rb = nb * 18;
+    return (size_t)(al1k(RW * rb) + al1k(MC * K + QK_K) + al1k(4 * (MC * nb + 8)) + 4 * (int64_t)RW * MC * nb);
+}
+template <int MC, int PRO = 0>
+__global__ __launch_bounds__(256) void k_gemv_q4_0s(GemvJob j, int RW) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nb = (int)(j.K / QK4_0), nbp = nb >> 1;
+    const int64_t rb = j.w_row_bytes;
+    const int mat = blockIdx.y;
+    const int64_t row0 = (int64_t)blockIdx.x * RW;
+    const int rows = (int)((j.N - row0) < RW ? (j.N - row0) : RW);
+    const int M = j.M;
+    char * ws = smem;
+    int8_t * xq_s = (int8_t *)(smem + al1k(RW * rb));
+    float * xd_s = (float *)((char *)xq_s + al1k(MC * j.K + QK_K));
+    float * T = (float *)((char *)xd_s + al1k(4 * (MC * nb + 8)));
+    const char * slab = (const char *)j.W[mat] + row0 * rb;
+    auto dma_slab = [&]() { dma_span(ws, slab, rows * rb, wave, 4, lane); };
+    if constexpr (PRO != 0) {
+        struct Mid {
+            decltype(dma_slab) & f;
+            __device__ void operator()() const { f(); }
+        };
+        q4k_prologue<PRO, 16, false, Mid, true>(j, (int)(j.K / QK_K), xq_s, xd_s, nullptr, nullptr, nullptr, Mid{dma_slab});
+    } else {
+        dma_slab();
+        dma_span((char *)xq_s, (const char *)j.aq.qs, (int64_t)M * j.K, wave, 4, lane);
+        dma_span((char *)xd_s, (const char *)j.aq.d, (int64_t)4 * M * nb, wave, 4, lane);
+    }
+    __builtin_amdgcn_s_waitcnt(0);  // this wave's DMA has landed (vmcnt, lgkmcnt 0)
+    __syncthreads();
+    for (int u = threadIdx.x; u < rows * nbp; u += 256) {
+        const int r = u / nbp, k = u - r * nbp;
+        const uint32_t * wl = (const uint32_t *)(ws + r * rb + 36 * k);
+        uint32_t w[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) w[i] = wl[i];
+        const float d0 = dev_fp16_to_fp32((uint16_t)(w[0] & 0xFFFFu));
+        const float d1 = dev_fp16_to_fp32((uint16_t)(w[4] >> 16));
+        uint32_t qs0[4], qs1[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            qs0[i] = __builtin_amdgcn_alignbit(w[i + 1], w[i], 16);
+            qs1[i] = w[5 + i];
+        }
+        int q0[8], q1[8];
+        q40_unpack(qs0, q0);
+        q40_unpack(qs1, q1);
+#pragma unroll
+        for (int m = 0; m < MC; ++m) {
+            if (m >= M) break;
+            const int4 * xb = (const int4 *)(xq_s + (m * nb + 2 * k) * QK8_0);
+            const int s0 = q50_dot(q0, xb[0], xb[1]);
+            const int s1 = q50_dot(q1, xb[2], xb[3]);
+            const float2 xd = *(const float2 *)(xd_s + m * nb + 2 * k);
+            float2 t;
+            t.x = q40_term(s0, d0, xd.x);
+            t.y = q40_term(s1, d1, xd.y);
+            *(float2 *)(T + (r * MC + m) * nb + 2 * k) = t;
+        }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < rows * MC; t += 256) {
+        const int r = t / MC, m = t % MC;
+        if (m >= M) continue;
+        const float4 * tr = (const float4 *)(T + (r * MC + m) * nb);
+        float a = 0.f;
+        for (int b = 0; b < (nb >> 2); ++b) {
+            const float4 v = tr[b];
+            a = __fadd_rn(a, v.x);
+            a = __fadd_rn(a, v.y);
+            a = __fadd_rn(a, v.z);
+            a = __fadd_rn(a, v.w);
+        }
+        gemv_store<MC>(j, mat, row0 + r, m, a);
+    }
+}
+
 // F32 / F16 GEMV: f32 products, f64 accumulation (ggml_vec_dot_f32 / _f16 generic), a wave per
 // row, 16-B loads.  For F16 the activation was rounded to fp16 first (vec_dot_type F16).
 template <int MC, bool F16>
@@ -2429,6 +2597,7 @@ size_t act_quant_bytes(int wtype, int64_t K, int64_t M) {
     auto al = [](size_t n) { return (n + 255) & ~(size_t)255; };
     switch (wtype) {
         case TTS_TYPE_Q4_K: return al(K * M) + al(sizeof(float) * M * (K / QK_K)) + al(sizeof(int32_t) * M * (K / 32));
+        case TTS_TYPE_Q4_0:
         case TTS_TYPE_Q5_0:  // vec_dot_type Q8_0
         case TTS_TYPE_Q8_0: return al(K * M) + al(sizeof(float) * M * (K / QK8_0));
         case TTS_TYPE_F16: return al(2 * K * M);
@@ -3308,6 +3477,93 @@ __global__ __launch_bounds__(256) void k_gemm_q5_0(GemvJob j) {
         }
 }
 
+// Q4_0 x Q8_0 GEMM for many columns: k_gemm_q5_0 with the 18-B block, no fifth bit and ggml's Q4_0 term
+// ((float)sumi * d_w) * d_x.  Lane group kq holds weights 8 kq .. 8 kq + 7: groups 0, 1 the low nibbles of
+// qs[0..7] / qs[8..15], groups 2, 3 their high nibbles, each made q - 8 by q40_s8.  Native rows (2-B aligned):
+// the eight qs bytes as four 16-bit loads.
+__global__ __launch_bounds__(256) void k_gemm_q4_0(GemvJob j) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int mat = blockIdx.z;
+    const int nb = (int)(j.K / QK4_0);
+    const int64_t r0 = (int64_t)blockIdx.x * 64 + (wave & 1) * 32;
+    const int64_t c0 = (int64_t)blockIdx.y * 64 + (wave >> 1) * 32;
+    const int r16 = lane & 15, kq = lane >> 4;
+    const int nsh = (kq >> 1) * 4;  // high nibbles for weights 16 .. 31
+    const uint8_t * W = j.W[mat];
+    const uint8_t * wrow[2];
+    const int8_t * xcol[2];
+    const float * xd[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int64_t r = min(r0 + 16 * t + r16, j.N - 1);
+        const int64_t c = min(c0 + 16 * t + r16, j.M - 1);
+        wrow[t] = W + r * j.w_row_bytes;
+        xcol[t] = j.aq.qs + c * j.K;
+        xd[t] = j.aq.d + c * nb;
+    }
+    // rows of this lane's accumulator elements (t, e): r0 + 16 t + 4 kq + e
+    const uint8_t * drow[2][4];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) drow[t][e] = W + min(r0 + 16 * t + 4 * kq + e, j.N - 1) * j.w_row_bytes;
+    float acc[2][2][4];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[a][b][e] = 0.0f;
+    long av[2], bv[2], an[2], bn[2];
+    float dwv[2][4], dxv[2], dwn[2][4], dxn[2];
+    auto load = [&](int b, long (&fa)[2], long (&fb)[2], float (&fw)[2][4], float (&fx)[2]) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const uint8_t * blk = wrow[t] + (int64_t)b * 18;
+            const uint16_t * q = (const uint16_t *)(blk + 2 + 8 * (kq & 1));
+            const uint32_t q0 = (uint32_t)q[0] | ((uint32_t)q[1] << 16), q1 = (uint32_t)q[2] | ((uint32_t)q[3] << 16);
+            const uint32_t lo = q40_s8((q0 >> nsh) & 0x0F0F0F0Fu);
+            const uint32_t hi = q40_s8((q1 >> nsh) & 0x0F0F0F0Fu);
+            fa[t] = (long)(((uint64_t)hi << 32) | lo);
+            fb[t] = *(const long *)(xcol[t] + (int64_t)b * QK8_0 + 8 * kq);
+            fx[t] = xd[t][b];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) fw[t][e] = dev_fp16_to_fp32(*(const uint16_t *)(drow[t][e] + (int64_t)b * 18));
+        }
+    };
+    load(0, av, bv, dwv, dxv);
+    for (int b = 0; b < nb; ++b) {
+        if (b + 1 < nb) load(b + 1, an, bn, dwn, dxn);
+#pragma unroll
+        for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+            for (int tj = 0; tj < 2; ++tj) {
+                const i32x4_t z = {0, 0, 0, 0};
+                const i32x4_t s = __builtin_amdgcn_mfma_i32_16x16x32_i8(av[ti], bv[tj], z, 0, 0, 0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[ti][tj][e] = __fadd_rn(acc[ti][tj][e], q40_term(s[e], dwv[ti][e], dxv[tj]));
+            }
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            av[t] = an[t], bv[t] = bn[t], dxv[t] = dxn[t];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dwv[t][e] = dwn[t][e];
+        }
+    }
+#pragma unroll
+    for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < 2; ++tj) {
+            const int64_t col = c0 + 16 * tj + r16;
+            if (col >= j.M) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t row = r0 + 16 * ti + 4 * kq + e;
+                if (row < j.N) gemv_store<1>(j, mat, row, (int)col, acc[ti][tj][e]);
+            }
+        }
+}
+
 // The staged form (K % 256 == 0, 16-B aligned weight rows and activation copy): a workgroup owns a
 // 64-row x TC-column output tile; the K dimension runs in stages of 8 blocks (256 elements), each
 // stage's operands fetched into registers while the previous stage computes, then stored to the other
@@ -3711,6 +3967,201 @@ static void launch_q50s(tts_hip_backend * be, const GemvJob & j) {
     if (be->profile_gemv) profile_push(be, e0, e1, gemv_bytes(j), TTS_TYPE_Q5_0);
 }
 
+// The staged Q4_0 GEMM (K % 256 == 0, 16-B aligned weight rows and activation copy): k_gemm_q5_0s with the
+// A operand unpacked as in k_gemm_q4_0.  A stage is 8 blocks: the 64 rows' native 144-B spans, row-major
+// (576 16-B chunks = 9 per row, fetched as 3 x 64 per wave: the 192 slots past 576 re-read the last chunk into
+// slack, which measured faster on weights from HBM than nine groups split 3 / 2 / 2 / 2 over the waves, DESIGN
+// 7g; row stride 36 dwords puts the 16 rows an MFMA reads 4 banks apart, and a lane reads 3 dwords); a lane's
+// eight qs bytes are two funnel-shifted dwords (they start 0 or 2 B off a dword), the rows' fp16 d single reads.
+// The third dword of the last row's last block lies in the slack and is shifted out.  B and dx as Q8s.
+// LDS: 2 x (12 + TC / 4 + TC / 32) KB = 96 KB at TC = 128, 60 KB at TC = 64.
+template <int TC>
+struct Q4s {
+    static constexpr int A_CHUNKS = 64 * 9;    // 64 rows x 144 B
+    static constexpr int A_BYTES = 12 * 1024;  // as 12 x 64 uniform 16-B chunks, three per wave (the last 3 x 64 are slack)
+    static constexpr int B_BYTES = TC * 256;
+    static constexpr int D_BYTES = TC * 32;
+    static constexpr int STAGE = A_BYTES + B_BYTES + D_BYTES;
+};
+template <int TC>
+__global__ __launch_bounds__(256) void k_gemm_q4_0s(GemvJob j) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int NT = TC / 32;  // 16-column tiles per wave
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int l16 = lane & 15, kq = lane >> 4;
+    const int nsh = (kq >> 1) * 4;  // high nibbles for weights 16 .. 31
+    const int mat = blockIdx.z;
+    const int64_t row0 = (int64_t)blockIdx.x * 64, col0 = (int64_t)blockIdx.y * TC;
+    const int64_t rb = j.w_row_bytes, K = j.K;
+    const int nb = (int)(K / QK4_0), nst = nb / 8;
+    const char * W = (const char *)j.W[mat];
+    const char * xq = (const char *)j.aq.qs;
+    const char * xdg = (const char *)j.aq.d;
+    // a wave's share of one stage: 3 A chunks, TC / 16 B chunks, <= 1 dx chunk, through registers (Q8s)
+    constexpr int NB_ = TC / 16;
+    u32x4 ra[3], rbv[NB_], rd;
+    auto stage_load = [&](int st) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            // A: linear chunk n = r * 9 + q (n < 576; the rest re-read the last chunk into the slack), every wave
+            // three unconditional loads
+            int n = (wave * 3 + i) * 64 + lane;
+            n = n < Q4s<TC>::A_CHUNKS ? n : Q4s<TC>::A_CHUNKS - 1;
+            const int r = n / 9, q = n - 9 * r;
+            const int64_t row = row0 + r < j.N ? row0 + r : j.N - 1;
+            ra[i] = *gptr((const u32x4 *)(W + row * rb + (int64_t)st * 144 + 16 * q));
+        }
+#pragma unroll
+        for (int i = 0; i < NB_; ++i) {
+            // B: slot idx = c * 16 + q' holds chunk q = q' ^ (c & 15) of column c
+            const int idx = (wave * NB_ + i) * 64 + lane, c = idx >> 4, q = (idx & 15) ^ (c & 15);
+            const int64_t col = col0 + c < j.M ? col0 + c : j.M - 1;
+            rbv[i] = *gptr((const u32x4 *)(xq + col * K + (int64_t)st * 256 + 16 * q));
+        }
+        {
+            // dx: column c's 8 scales as chunks 2c, 2c + 1 (waves 0 .. TC/32 - 1)
+            const int idx = (wave < TC / 32 ? wave : 0) * 64 + lane, c = idx >> 1, h = idx & 1;
+            const int64_t col = col0 + c < j.M ? col0 + c : j.M - 1;
+            rd = *gptr((const u32x4 *)(xdg + col * (int64_t)nb * 4 + (int64_t)st * 32 + 16 * h));
+        }
+    };
+    auto stage_store = [&](int buf) __attribute__((always_inline)) {
+        char * base = smem + buf * Q4s<TC>::STAGE;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) *(u32x4 *)(base + (wave * 3 + i) * 1024 + 16 * lane) = ra[i];
+        char * bb = base + Q4s<TC>::A_BYTES;
+#pragma unroll
+        for (int i = 0; i < NB_; ++i) *(u32x4 *)(bb + (wave * NB_ + i) * 1024 + 16 * lane) = rbv[i];
+        if (wave < TC / 32) *(u32x4 *)(bb + Q4s<TC>::B_BYTES + wave * 1024 + 16 * lane) = rd;
+    };
+    const int wr = (wave & 1) * 32, wc = (wave >> 1) * (TC / 2);
+    float acc[2][NT][4];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < NT; ++b)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[a][b][e] = 0.0f;
+    stage_load(0);
+    stage_store(0);
+    __syncthreads();
+    for (int st = 0; st < nst; ++st) {
+        stage_load(st + 1 < nst ? st + 1 : st);  // unconditional (clamped): lands during this stage's MFMAs
+        const char * base = smem + (st & 1) * Q4s<TC>::STAGE;
+        const char * bb = base + Q4s<TC>::A_BYTES;
+        const float * db = (const float *)(bb + Q4s<TC>::B_BYTES);
+#pragma unroll 2
+        for (int b = 0; b < 8; ++b) {
+            long av[2], bv[NT];
+            float dw[2][4], dx[NT];
+#pragma unroll
+            for (int ti = 0; ti < 2; ++ti) {
+                const int off = (wr + 16 * ti + l16) * 144 + b * 18 + 2 + 8 * (kq & 1);
+                const uint32_t * p = (const uint32_t *)(base + (off & ~3));
+                const uint32_t d0 = p[0], d1 = p[1], d2 = p[2];
+                const uint32_t sh = (off & 3) * 8;
+                const uint32_t q0 = __builtin_amdgcn_alignbit(d1, d0, sh), q1 = __builtin_amdgcn_alignbit(d2, d1, sh);
+                const uint32_t lo = q40_s8((q0 >> nsh) & 0x0F0F0F0Fu);
+                const uint32_t hi = q40_s8((q1 >> nsh) & 0x0F0F0F0Fu);
+                av[ti] = (long)(((uint64_t)hi << 32) | lo);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    dw[ti][e] = dev_fp16_to_fp32(*(const uint16_t *)(base + (wr + 16 * ti + 4 * kq + e) * 144 + b * 18));
+            }
+#pragma unroll
+            for (int tj = 0; tj < NT; ++tj) {
+                const int c = wc + 16 * tj + l16;
+                const int q = 2 * b + (kq >> 1);
+                bv[tj] = *(const long *)(bb + (c * 16 + (q ^ (c & 15))) * 16 + 8 * (kq & 1));
+                dx[tj] = db[c * 8 + b];
+            }
+            i32x4_t sv[2][NT];
+#pragma unroll
+            for (int tj = 0; tj < NT; ++tj)
+#pragma unroll
+                for (int ti = 0; ti < 2; ++ti) {
+                    const i32x4_t z = {0, 0, 0, 0};
+                    sv[ti][tj] = __builtin_amdgcn_mfma_i32_16x16x32_i8(av[ti], bv[tj], z, 0, 0, 0);
+                }
+            __builtin_amdgcn_sched_barrier(0);  // keep the scheduler from re-serializing them into one accumulator
+#pragma unroll
+            for (int tj = 0; tj < NT; ++tj)
+#pragma unroll
+                for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[ti][tj][e] = __fadd_rn(acc[ti][tj][e], q40_term(sv[ti][tj][e], dw[ti][e], dx[tj]));
+        }
+        // every wave is done with the other buffer (stage st - 1) since the last barrier
+        if (st + 1 < nst) stage_store((st + 1) & 1);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < NT; ++tj) {
+            const int64_t col = col0 + wc + 16 * tj + l16;
+            if (col >= j.M) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t row = row0 + wr + 16 * ti + 4 * kq + e;
+                if (row < j.N) gemv_store<1>(j, mat, row, (int)col, acc[ti][tj][e]);
+            }
+        }
+}
+
+// Q4_0: the same two beside them, on its own options
+static void launch_gemm_q4_0(tts_hip_backend * be, const GemvJob & j) {
+    bool staged = be->gemm_q4_0_staged > 0 && j.K % QK_K == 0 && j.w_row_bytes % 16 == 0 && !((uintptr_t)j.aq.qs & 15) && !((uintptr_t)j.aq.d & 15);
+    for (int m = 0; m < j.nmat; ++m) staged = staged && !((uintptr_t)j.W[m] & 15);
+    if (staged) {
+        static std::atomic<uint32_t> attr_done[2];
+        if (be->gemm_q4_0_staged == 1) {
+            set_lds_attr_once(attr_done[0], be->device, (const void *)k_gemm_q4_0s<64>);
+            const dim3 grid((unsigned)((j.N + 63) / 64), (unsigned)((j.M + 63) / 64), (unsigned)j.nmat);
+            hipLaunchKernelGGL(k_gemm_q4_0s<64>, grid, dim3(256), 2 * Q4s<64>::STAGE, be->stream, j);
+        } else {
+            set_lds_attr_once(attr_done[1], be->device, (const void *)k_gemm_q4_0s<128>);
+            const dim3 grid((unsigned)((j.N + 63) / 64), (unsigned)((j.M + 127) / 128), (unsigned)j.nmat);
+            hipLaunchKernelGGL(k_gemm_q4_0s<128>, grid, dim3(256), 2 * Q4s<128>::STAGE, be->stream, j);
+        }
+        return;
+    }
+    const dim3 grid((unsigned)((j.N + 63) / 64), (unsigned)((j.M + 63) / 64), (unsigned)j.nmat);
+    hipLaunchKernelGGL(k_gemm_q4_0, grid, dim3(256), 0, be->stream, j);
+}
+
+static bool q40s_ok(const tts_hip_backend * be, const GemvJob & j) {
+    if (!be->gemv_q40_slab || j.K % QK_K || j.hetero || j.dbg) return false;
+    if (!j.pro && (j.aq.vtype != TTS_TYPE_Q8_0 || ((uintptr_t)j.aq.qs & 15) || ((uintptr_t)j.aq.d & 15))) return false;
+    for (int m = 0; m < j.nmat; ++m)
+        if ((uintptr_t)j.W[m] & 15) return false;
+    return q40s_lds(8, j.K, 1) <= 160 * 1024;
+}
+template <int MC>
+static void launch_q40s(tts_hip_backend * be, const GemvJob & j) {
+    // rows per workgroup as launch_q80s chooses them (option TTS_HIP_OPT_GEMV_Q40_RW overrides)
+    int RW = be->gemv_q40_rw > 0 ? be->gemv_q40_rw : 32;
+    if (be->gemv_q40_rw <= 0)
+        while (RW > 1 && (j.N + RW - 1) / RW * j.nmat < be->cus) RW /= 2;
+    while (RW > 1 && q40s_lds(MC, j.K, RW) > (be->gemv_q40_rw > 0 ? 160 : 80) * 1024) RW /= 2;  // auto: 2+ workgroups per CU
+    const size_t lds = q40s_lds(MC, j.K, RW);
+    const dim3 grid((unsigned)((j.N + RW - 1) / RW), (unsigned)j.nmat);
+    static std::atomic<uint32_t> attr_done[3];
+    hipEvent_t e0 = nullptr, e1 = nullptr;  // profiled: in-packet events, as the Q8_0 slab
+    if (be->profile_gemv) profile_pair(be, e0, e1);
+    if (j.pro == PRO_LN) {
+        set_lds_attr_once(attr_done[2], be->device, (const void *)k_gemv_q4_0s<MC, PRO_LN>);
+        hipExtLaunchKernelGGL((k_gemv_q4_0s<MC, PRO_LN>), grid, dim3(256), (uint32_t)lds, be->stream, e0, e1, 0u, j, RW);
+    } else if (j.pro == PRO_QUANT) {
+        set_lds_attr_once(attr_done[1], be->device, (const void *)k_gemv_q4_0s<MC, PRO_QUANT>);
+        hipExtLaunchKernelGGL((k_gemv_q4_0s<MC, PRO_QUANT>), grid, dim3(256), (uint32_t)lds, be->stream, e0, e1, 0u, j, RW);
+    } else {
+        set_lds_attr_once(attr_done[0], be->device, (const void *)k_gemv_q4_0s<MC>);
+        hipExtLaunchKernelGGL(k_gemv_q4_0s<MC>, grid, dim3(256), (uint32_t)lds, be->stream, e0, e1, 0u, j, RW);
+    }
+    if (be->profile_gemv) profile_push(be, e0, e1, gemv_bytes(j), TTS_TYPE_Q4_0);
+}
+
 template <int MC>
 static void launch_gemv_mc(tts_hip_backend * be, const GemvJob & j) {
     const unsigned nmat = (unsigned)j.nmat;
@@ -3728,6 +4179,19 @@ static void launch_gemv_mc(tts_hip_backend * be, const GemvJob & j) {
             if (j.pro == PRO_LN) hipLaunchKernelGGL((k_gemv_q5_0<MC, PRO_LN>), dim3(grid, nmat), dim3(256), lds, be->stream, j, RW);
             else if (j.pro == PRO_QUANT) hipLaunchKernelGGL((k_gemv_q5_0<MC, PRO_QUANT>), dim3(grid, nmat), dim3(256), lds, be->stream, j, RW);
             else hipLaunchKernelGGL(k_gemv_q5_0<MC>, dim3(grid, nmat), dim3(256), lds, be->stream, j, RW);
+        } break;
+        case TTS_TYPE_Q4_0: {
+            if (q40s_ok(be, j)) {
+                launch_q40s<MC>(be, j);
+                break;
+            }
+            int RW = 8;  // the general kernel's LDS layout is k_gemv_q8_0's
+            while (RW > 1 && q80_lds(MC, j.K, RW) > 64 * 1024) RW /= 2;
+            const size_t lds = q80_lds(MC, j.K, RW) + (j.pro ? QK_K + 64 : 0);
+            const unsigned grid = (unsigned)((j.N + RW - 1) / RW);
+            if (j.pro == PRO_LN) hipLaunchKernelGGL((k_gemv_q4_0<MC, PRO_LN>), dim3(grid, nmat), dim3(256), lds, be->stream, j, RW);
+            else if (j.pro == PRO_QUANT) hipLaunchKernelGGL((k_gemv_q4_0<MC, PRO_QUANT>), dim3(grid, nmat), dim3(256), lds, be->stream, j, RW);
+            else hipLaunchKernelGGL(k_gemv_q4_0<MC>, dim3(grid, nmat), dim3(256), lds, be->stream, j, RW);
         } break;
         case TTS_TYPE_Q8_0: {
             if (q80s_ok(be, j)) {
@@ -3768,9 +4232,10 @@ void launch_profile_spin(tts_hip_backend * be, double us) {
 }
 
 void launch_gemv_job(tts_hip_backend * be, const GemvJob & job) {
-    // Q4_K launches and Q8_0 / Q5_0 slab GEMVs profile themselves (in-packet events); other jobs are timed whole
+    // Q4_K launches and Q8_0 / Q5_0 / Q4_0 slab GEMVs profile themselves (in-packet events); other jobs are timed whole
     const bool prof = be->profile_gemv && job.wtype != TTS_TYPE_Q4_K && !(job.wtype == TTS_TYPE_Q8_0 && job.M <= 8 && q80s_ok(be, job)) &&
-                      !(job.wtype == TTS_TYPE_Q5_0 && job.M <= 8 && q50s_ok(be, job));
+                      !(job.wtype == TTS_TYPE_Q5_0 && job.M <= 8 && q50s_ok(be, job)) &&
+                      !(job.wtype == TTS_TYPE_Q4_0 && job.M <= 8 && q40s_ok(be, job));
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (prof) {
         profile_pair(be, e0, e1);
@@ -3796,6 +4261,15 @@ void launch_gemv_job(tts_hip_backend * be, const GemvJob & job) {
     }
     if (job.wtype == TTS_TYPE_Q5_0 && job.M > 8 && job.aq.vtype == TTS_TYPE_Q8_0 && !job.hetero && be->gemm_q5) {
         launch_gemm_q5_0(be, job);  // one matrix-core pass instead of a GEMV launch per 8 columns
+        TTS_HIP_CHECK(hipGetLastError());
+        if (prof) {
+            TTS_HIP_CHECK(hipEventRecord(e1, be->stream));
+            profile_push(be, e0, e1, gemv_bytes(job), job.wtype);
+        }
+        return;
+    }
+    if (job.wtype == TTS_TYPE_Q4_0 && job.M > 8 && job.aq.vtype == TTS_TYPE_Q8_0 && !job.hetero && be->gemm_q4_0) {
+        launch_gemm_q4_0(be, job);  // one matrix-core pass instead of a GEMV launch per 8 columns
         TTS_HIP_CHECK(hipGetLastError());
         if (prof) {
             TTS_HIP_CHECK(hipEventRecord(e1, be->stream));

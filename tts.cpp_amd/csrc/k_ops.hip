@@ -288,7 +288,7 @@ __global__ __launch_bounds__(256) void k_soft_max(TD dst, TD a, TD m, int mask_f
     for (int64_t i = threadIdx.x; i < nc; i += blockDim.x) dp[i] = __fmul_rn(dp[i], inv);
 }
 
-// ---- GET_ROWS (f32 / f16 / q4_K / q8_0 / q5_0 source, i32 index) ----
+// ---- GET_ROWS (f32 / f16 / q4_K / q8_0 / q5_0 / q4_0 source, i32 index) ----
 // element k of a table row (dequantize_row_q4_K / q8_0 / q5_0 arithmetic for quantized tables)
 __device__ __forceinline__ float table_elem(const TD & s0, const char * src, int64_t k) {
     if (s0.type == TTS_TYPE_F32) return ((const float *)src)[k];
@@ -303,6 +303,12 @@ __device__ __forceinline__ float table_elem(const TD & s0, const char * src, int
         const int nib = e < 16 ? (b->qs[jq] & 0x0F) : (b->qs[jq] >> 4);
         const int hb = (b->qh[e >> 3] >> (e & 7)) & 1;
         return __fmul_rn((float)((nib | (hb << 4)) - 16), __half2float(__ushort_as_half(b->d)));
+    }
+    if (s0.type == TTS_TYPE_Q4_0) {  // dequantize_row_q4_0: element j / j + 16 from qs[j]'s low / high nibble, less 8
+        const block_q4_0 * b = (const block_q4_0 *)src + k / QK4_0;
+        const int e = (int)(k % QK4_0), jq = e & 15;
+        const int nib = e < 16 ? (b->qs[jq] & 0x0F) : (b->qs[jq] >> 4);
+        return __fmul_rn((float)(nib - 8), __half2float(__ushort_as_half(b->d)));
     }
     // Q4_K: dequantize_row_q4_K
     const block_q4_K * b = (const block_q4_K *)src + k / QK_K;

@@ -1,6 +1,7 @@
-// Weight quantizers on the device: ggml's quantize_row_q4_K_ref, quantize_row_q8_0_ref and quantize_row_q5_0_ref
+// Weight quantizers on the device: ggml's quantize_row_q4_K_ref, quantize_row_q8_0_ref, quantize_row_q5_0_ref and
+// quantize_row_q4_0_ref
 // (ggml-quants.c; restated in oracle/ggml_ref.c), so f32 weights can be turned into GGUF-compatible
-// Q4_K / Q8_0 / Q5_0 bytes where they live (the reference's examples/quantize path, quantize_impl.cpp:82-292,
+// Q4_K / Q8_0 / Q5_0 / Q4_0 bytes where they live (the reference's examples/quantize path, quantize_impl.cpp:82-292,
 // does this on the CPU).  Every float operation is the reference's, in source order, rounded to f32
 // (-ffp-contract=off; sqrt and division correctly rounded), so the bytes equal the CPU's.
 //
@@ -237,6 +238,31 @@ __global__ __launch_bounds__(256) void k_quantize_q5_0(const float * __restrict_
     y[2] = (uint8_t)qh, y[3] = (uint8_t)(qh >> 8), y[4] = (uint8_t)(qh >> 16), y[5] = (uint8_t)(qh >> 24);
 }
 
+// quantize_row_q4_0_ref: one thread per 32-value block.  max = the signed value of largest magnitude (the
+// first of equals), d = max / -8, id = d ? 1 / d : 0, q = min(15, (int8_t)(x * id + 8.5f)) (truncation);
+// elements j / j + 16 share qs[j] (low / high nibble).
+__global__ __launch_bounds__(256) void k_quantize_q4_0(const float * __restrict__ x, uint8_t * __restrict__ dst, int64_t rows, int64_t K) {
+    const int64_t nbr = K / 32, nblk = rows * nbr;
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= nblk) return;
+    const float * xs = x + (b / nbr) * K + (b % nbr) * 32;
+    float amax = 0.0f, vmax = 0.0f;
+    for (int j = 0; j < 32; ++j) {
+        const float v = xs[j];
+        if (amax < fabsf(v)) amax = fabsf(v), vmax = v;
+    }
+    const float d = cr_divf(vmax, -8.f);
+    const float id = d != 0.f ? cr_divf(1.0f, d) : 0.0f;
+    uint8_t * y = dst + b * 18;
+    const uint16_t dh = q_fp32_to_fp16(d);
+    y[0] = (uint8_t)(dh & 0xFF), y[1] = (uint8_t)(dh >> 8);
+    for (int j = 0; j < 16; ++j) {
+        const int q0 = min(15, (int)(int8_t)__fadd_rn(__fmul_rn(xs[j], id), 8.5f));
+        const int q1 = min(15, (int)(int8_t)__fadd_rn(__fmul_rn(xs[j + 16], id), 8.5f));
+        y[2 + j] = (uint8_t)((q0 & 0x0F) | ((q1 & 0x0F) << 4));
+    }
+}
+
 }  // namespace
 
 }  // namespace tts
@@ -256,6 +282,10 @@ extern "C" int tts_hip_quantize(tts_hip_backend_t be, int type, const float * x,
         if (K % 32) return TTS_STATUS_BAD_ARG;
         const int64_t nblk = rows * (K / 32);
         hipLaunchKernelGGL(tts::k_quantize_q5_0, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, be->stream, x, (uint8_t *)dst, rows, K);
+    } else if (type == TTS_TYPE_Q4_0) {
+        if (K % 32) return TTS_STATUS_BAD_ARG;
+        const int64_t nblk = rows * (K / 32);
+        hipLaunchKernelGGL(tts::k_quantize_q4_0, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, be->stream, x, (uint8_t *)dst, rows, K);
     } else {
         return TTS_STATUS_UNSUPPORTED;
     }

@@ -93,7 +93,7 @@ static tts_tensor * wnew(tts_kokoro_gen * k, float scale, float offset, int64_t 
                          bool gguf = true) {
     int ty = gguf ? kokoro_tensor_type(k->cfg.weight_type, k->cfg.f16_rest, name, ne0, ne1, nullptr) : TTS_TYPE_F32;
     if (gguf) ty = kokoro_store_type(k->w, ty, name, ne0, ne1, &k->type_err);
-    const weight_fill fill = ty == TTS_TYPE_Q8_0 || ty == TTS_TYPE_Q5_0 ? weight_fill::matrix(scale / std::sqrt(3.0f)) : weight_fill::uniform(scale, offset);
+    const weight_fill fill = wtype_q80_act(ty) ? weight_fill::matrix(scale / std::sqrt(3.0f)) : weight_fill::uniform(scale, offset);
     return k->w.add(ty, ne0, ne1, ne2, name, fill, k->cfg.seed ^ k->w.index(), gguf);
 }
 
@@ -143,7 +143,7 @@ uint64_t kokoro_read_weight(const tts_backend_iface & be, const tts_tensor * t, 
         for (size_t i = 0; i < h.size(); ++i) dst[i] = fp16_to_fp32_host(h[i]);
         return n;
     }
-    if (t->type == TTS_TYPE_Q8_0 || t->type == TTS_TYPE_Q5_0) {
+    if (wtype_q80_act(t->type)) {
         std::vector<uint8_t> q(tg::nbytes(t));
         if (be.get(be.ctx, q.data(), t->data, q.size()) != 0) return 0;
         const size_t nblk = (size_t)tg::nelements(t) / 32;
@@ -153,6 +153,13 @@ uint64_t kokoro_read_weight(const tts_backend_iface & be, const tts_tensor * t, 
                 const block_q8_0 * x = (const block_q8_0 *)q.data() + b;
                 const float d = fp16_to_fp32_host(x->d);
                 for (int j = 0; j < 32; ++j) y[j] = x->qs[j] * d;
+            } else if (t->type == TTS_TYPE_Q4_0) {  // dequantize_row_q4_0
+                const block_q4_0 * x = (const block_q4_0 *)q.data() + b;
+                const float d = fp16_to_fp32_host(x->d);
+                for (int j = 0; j < 16; ++j) {
+                    y[j] = (float)((x->qs[j] & 0x0F) - 8) * d;
+                    y[j + 16] = (float)((x->qs[j] >> 4) - 8) * d;
+                }
             } else {  // dequantize_row_q5_0
                 const block_q5_0 * x = (const block_q5_0 *)q.data() + b;
                 const float d = fp16_to_fp32_host(x->d);

@@ -41,13 +41,13 @@ inline bool kokoro_f16_tensor(const std::string & name, int64_t ne1) {
 }
 
 // The storage type of tensor `name` ([ne0, ne1, ..]; ne1 = 0: 1-D) under a runner's weight_type / f16_rest:
-//  * weight_type Q8_0 / Q5_0: that type exactly where the quantize tool's Kokoro rule quantizes
+//  * weight_type Q8_0 / Q5_0 / Q4_0: that type exactly where the quantize tool's Kokoro rule quantizes
 //    (tts_gguf_tensor_rule("kokoro", "kokoro." + name) == 1, quantize_impl.cpp:20-40) and the tensor is a
 //    matrix; *bad_row is set when such a row is no whole number of 32-element blocks;
 //  * weight_type F16, or f16_rest (`quantize -nqf`): F16 for the kokoro_f16_tensor tensors not quantized;
 //  * F32 otherwise.
 inline int kokoro_tensor_type(int weight_type, int f16_rest, const std::string & name, int64_t ne0, int64_t ne1, bool * bad_row) {
-    if ((weight_type == TTS_TYPE_Q8_0 || weight_type == TTS_TYPE_Q5_0) && ne1 > 0) {
+    if (wtype_q80_act(weight_type) && ne1 > 0) {
         tts_quantize_params qp;
         memset(&qp, 0, sizeof(qp));
         qp.quantize_type = weight_type;
@@ -60,14 +60,14 @@ inline int kokoro_tensor_type(int weight_type, int f16_rest, const std::string &
 }
 
 // With a file attached to the store the tensor takes the type the file gives it (missing: F32, and upload()
-// reports it): F32 anywhere, F16 where kokoro_f16_tensor allows, Q8_0 / Q5_0 where the rule quantizes.  Any other
+// reports it): F32 anywhere, F16 where kokoro_f16_tensor allows, Q8_0 / Q5_0 / Q4_0 where the rule quantizes.  Any other
 // type, or a quantized tensor the rule would not quantize (a bias, say), sets *err to the reason with the file's
 // tensor name.
 inline int kokoro_store_type(const weight_store & w, int synth_type, const std::string & name, int64_t ne0, int64_t ne1, std::string * err) {
     if (!w.gguf) return synth_type;
     const int ft = w.file_type(name, TTS_TYPE_F32);
     bool ok = ft == TTS_TYPE_F32 || (ft == TTS_TYPE_F16 && kokoro_f16_tensor(name, ne1));
-    if (ft == TTS_TYPE_Q8_0 || ft == TTS_TYPE_Q5_0) {
+    if (wtype_q80_act(ft)) {
         bool bad = false;
         ok = kokoro_tensor_type(ft, 0, name, ne0, ne1, &bad) == ft && !bad;
     }
@@ -83,7 +83,7 @@ int kokoro_gen_write(const tts_kokoro_gen_config * cfg, tts_gguf_writer * w);
 // The generator's fields of cfg from the file's keys and tensor shapes; false (reason on stderr) when one is missing.
 bool kokoro_gen_config_from_gguf(const tts_gguf * g, tts_kokoro_gen_config * cfg);
 
-// f32 values of a weight (F16 widened, Q8_0 / Q5_0 by ggml's dequantize_row_*) into dst; returns nelements * 4 (0 on a failed read)
+// f32 values of a weight (F16 widened, Q8_0 / Q5_0 / Q4_0 by ggml's dequantize_row_*) into dst; returns nelements * 4 (0 on a failed read)
 uint64_t kokoro_read_weight(const tts_backend_iface & be, const tts_tensor * t, float * dst, uint64_t cap);
 
 }  // namespace tts

@@ -19,7 +19,7 @@
 // recurrence into one kernel per step (graph_exec.hip try_lstm).
 // Weights are deterministic synthetic tensors in Kokoro-82M shapes (no checkpoints offline),
 // named as the GGUF converter names them (py-gguf/tts_encoders/kokoro_gguf_encoder.py), in the storage
-// types a file from the quantize tool holds: F32, F16, or Q8_0 / Q5_0 for the tensors its Kokoro rule
+// types a file from the quantize tool holds: F32, F16, or Q8_0 / Q5_0 / Q4_0 for the tensors its Kokoro rule
 // quantizes (kokoro_tensor_type, kokoro_gen.h).
 #include <chrono>
 #include <cmath>
@@ -136,7 +136,7 @@ static tts_tensor * wnew(tts_kokoro * k, float scale, float offset, int64_t ne0,
     int ty = gguf ? kokoro_tensor_type(k->cfg.weight_type, k->cfg.f16_rest, name, ne0, ne1, &bad) : TTS_TYPE_F32;
     if (gguf && k->w.gguf) bad = false, ty = kokoro_store_type(k->w, ty, name, ne0, ne1, &k->type_err);
     if (bad && k->bad_row.empty()) k->bad_row = name + " (rows of " + std::to_string(ne0) + ")";
-    const weight_fill fill = ty == TTS_TYPE_Q8_0 || ty == TTS_TYPE_Q5_0 ? weight_fill::matrix(scale / std::sqrt(3.0f)) : weight_fill::uniform(scale, offset);
+    const weight_fill fill = wtype_q80_act(ty) ? weight_fill::matrix(scale / std::sqrt(3.0f)) : weight_fill::uniform(scale, offset);
     return k->w.add(bad ? TTS_TYPE_F32 : ty, ne0, ne1, ne2, name, fill, k->cfg.seed ^ (k->w.index() * 0x9E3779B97F4A7C15ull), gguf);
 }
 
@@ -199,8 +199,8 @@ static bool config_ok(const tts_kokoro_config & c) {
     if (c.hidden % c.n_heads || c.d_model % 2 || c.max_tokens < 3 || c.max_tokens > c.max_context || c.max_total < 1 || c.n_decode < 1 ||
         c.te_kernel % 2 == 0 || c.n_dur_layers < 1 || c.te_depth < 0 || c.n_voice_rows < c.max_tokens - 2 || c.max_dur < 1)
         return false;
-    if (c.weight_type != TTS_TYPE_F32 && c.weight_type != TTS_TYPE_F16 && c.weight_type != TTS_TYPE_Q8_0 && c.weight_type != TTS_TYPE_Q5_0) {
-        fprintf(stderr, "kokoro: weight_type %d is not F32, F16, Q8_0 or Q5_0\n", c.weight_type);
+    if (c.weight_type != TTS_TYPE_F32 && c.weight_type != TTS_TYPE_F16 && c.weight_type != TTS_TYPE_Q8_0 && c.weight_type != TTS_TYPE_Q5_0 && c.weight_type != TTS_TYPE_Q4_0) {
+        fprintf(stderr, "kokoro: weight_type %d is not F32, F16, Q8_0, Q5_0 or Q4_0\n", c.weight_type);
         return false;
     }
     return true;

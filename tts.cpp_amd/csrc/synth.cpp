@@ -126,11 +126,27 @@ void synth_q5_0(void * dst, int64_t rows, int64_t K, uint64_t seed, float std) {
     });
 }
 
+void synth_q4_0(void * dst, int64_t rows, int64_t K, uint64_t seed, float std) {
+    const int64_t nblk = rows * (K / QK4_0);
+    block_q4_0 * b = (block_q4_0 *)dst;
+    const float d = std / 4.61f;  // U{-8..7} has std ~4.61
+    parallel_for((size_t)nblk, [&](size_t a, size_t e) {
+        for (size_t i = a; i < e; ++i) {
+            b[i].d = fp32_to_fp16_host(d * (0.75f + 0.5f * u01(synth_hash(seed, i * 3))));
+            for (int k = 0; k < 2; ++k) {
+                const uint64_t h = synth_hash(seed, i * 3 + 1 + k);
+                memcpy(b[i].qs + 8 * k, &h, 8);
+            }
+        }
+    });
+}
+
 void synth_fill(int type, void * dst, int64_t rows, int64_t K, uint64_t seed, float std) {
     switch (type) {
         case TTS_TYPE_Q4_K: synth_q4_K(dst, rows, K, seed, std); break;
         case TTS_TYPE_Q8_0: synth_q8_0(dst, rows, K, seed, std); break;
         case TTS_TYPE_Q5_0: synth_q5_0(dst, rows, K, seed, std); break;
+        case TTS_TYPE_Q4_0: synth_q4_0(dst, rows, K, seed, std); break;
         case TTS_TYPE_F16: synth_f16((uint16_t *)dst, (size_t)(rows * K), seed, std * 1.7320508f); break;
         default: synth_f32((float *)dst, (size_t)(rows * K), seed, std * 1.7320508f, 0.0f); break;
     }

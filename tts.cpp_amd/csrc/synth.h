@@ -17,6 +17,7 @@ void synth_f16(uint16_t * dst, size_t n, uint64_t seed, float scale);
 void synth_q4_K(void * dst, int64_t rows, int64_t K, uint64_t seed, float std);
 void synth_q8_0(void * dst, int64_t rows, int64_t K, uint64_t seed, float std);
 void synth_q5_0(void * dst, int64_t rows, int64_t K, uint64_t seed, float std);
+void synth_q4_0(void * dst, int64_t rows, int64_t K, uint64_t seed, float std);
 void synth_fill(int type, void * dst, int64_t rows, int64_t K, uint64_t seed, float std);
 
 }  // namespace tts

@@ -108,8 +108,9 @@ typedef struct tts_quantize_params {
 /* Rows of x [rows][K] f32 (host memory) -> type's blocks in dst (host memory); 0 on success. */
 typedef int (*tts_quantize_rows_fn)(void * ctx, int32_t type, const float * x, void * dst, int64_t rows, int64_t K);
 
-/* quantize_impl.cpp:14-80 (parler / dia / kokoro; orpheus: every ".weight" matrix except norms,
- * where the reference aborts): 1 = quantize, 2 = convert to F16, 0 = copy unchanged. */
+/* quantize_impl.cpp:14-80 (parler / dia / kokoro; orpheus, where the reference aborts: the projections
+ * orpheus.layers.N.{self_attn,mlp}.*_proj and orpheus.embed_tokens, orpheus.lm_head with quantize_output_heads,
+ * never a norm, orpheus.rope_frequencies or a snac.* tensor): 1 = quantize, 2 = convert to F16, 0 = copy unchanged. */
 int tts_gguf_tensor_rule(const char * arch, const char * name, const tts_quantize_params * params);
 /* quantize_gguf: KV pairs copied + general.quantization_version / general.quantization_type, every
  * tensor in file order, quantized rows from `fn`, F16 by round-to-nearest-even.  0 on success. */
@@ -144,6 +145,44 @@ int tts_t5_write_synthetic_gguf(const tts_t5_config * cfg, const char * path);
 int tts_dac_config_from_gguf(const tts_gguf * g, tts_dac_config * cfg);
 /* A DAC decoder whose weights are the file's "audio_encoder.*" tensors (F32). */
 tts_dac * tts_dac_create_from_gguf(const tts_backend_iface * be, const tts_dac_config * cfg, const tts_gguf * g);
+
+/* ---- Dia (dia_model::prep_constants / assign_weight, src/models/dia/model.cpp:3-251) ---- */
+/* general.architecture must be "dia".  The dia.* keys prep_constants reads (layers, heads, head size, vocabulary,
+ * context and generation lengths, dia.cfg_scale when present); the widths no key carries from the tensors: encoder
+ * hidden size and vocabulary from dia.encoder.embedding, FFN sizes from the gate tensors, decoder hidden size from
+ * dia.decoder.embeddings.0; weight_type from dia.decoder.layers.0.self_q_proj, head_type from dia.decoder.heads.0.
+ * seed and arena stay as given.  0 on success. */
+int tts_dia_config_from_gguf(const tts_gguf * g, tts_dia_config * cfg);
+/* A Dia runner whose weights are the file's "dia.*" tensors, each in the type the file gives it: F32, F16, Q8_0,
+ * Q5_0 or Q4_0 for the matrices, embeddings and heads (what the quantize tool's Dia rule can produce), F32 for the
+ * norms.  NULL (the tensor's name and the reason on stderr) on a missing tensor, a shape that disagrees with cfg,
+ * another type, or a quantized norm. */
+tts_dia * tts_dia_create_from_gguf(const tts_backend_iface * be, const tts_dia_config * cfg, const tts_gguf * g);
+/* Writes the runner's synthetic weights (the ones tts_dia_create uploads for cfg) under the reference's tensor
+ * names and keys, plus the DAC decoder ("audio_encoder.*", dac.* keys) for dac_cfg when not NULL: the file
+ * tts_dac_create_from_gguf loads its other half from. */
+int tts_dia_write_synthetic_gguf(const tts_dia_config * cfg, const tts_dac_config * dac_cfg, const char * path);
+
+/* ---- Orpheus (orpheus_model::prep_constants / assign_weight, src/models/orpheus/model.cpp:11-120) ---- */
+/* general.architecture must be "orpheus".  orpheus.{vocab_size,attn_heads,kv_attn_heads,head_dim,hidden_size,layers};
+ * ffn_size from orpheus.layers.0.mlp.gate_proj, weight_type from orpheus.layers.0.self_attn.q_proj.  batch, max_ctx,
+ * seed, the arena and the rope fields stay as given (the loader does not use the rope fields).  0 on success. */
+int tts_orpheus_config_from_gguf(const tts_gguf * g, tts_orpheus_config * cfg);
+/* An Orpheus runner whose weights are the file's "orpheus.*" tensors (names as the converter writes them, without
+ * ".weight").  The embedding, the head and every matrix take the type the file gives that tensor: F32, Q4_K, Q8_0,
+ * Q5_0 or Q4_0 (a file quantized without quantize_output_heads has an F32 lm_head beside quantized matrices); norms
+ * and orpheus.rope_frequencies, which is read from the file and not recomputed, are F32.  NULL on failure, as above. */
+tts_orpheus * tts_orpheus_create_from_gguf(const tts_backend_iface * be, const tts_orpheus_config * cfg, const tts_gguf * g);
+/* Writes the synthetic model under those names and keys, plus the SNAC decoder ("snac.*") for snac_cfg when not NULL. */
+int tts_orpheus_write_synthetic_gguf(const tts_orpheus_config * cfg, const tts_snac_config * snac_cfg, const char * path);
+
+/* ---- SNAC (snac_model::prep_constants / prep_layers / assign_weight, src/decoder/snac_model.cpp:3-84) ---- */
+/* snac.audio_token_channels, snac.snac_layer_stride_{i} (padding and grouping, when present, must be what the
+ * decoder assumes); codebook size and dimension, latent and decoder widths from the tensor shapes.  repeats,
+ * max_frames, seed and the arena stay as given.  0 on success. */
+int tts_snac_config_from_gguf(const tts_gguf * g, tts_snac_config * cfg);
+/* A SNAC decoder whose weights are the file's "snac.*" tensors (F32 only). */
+tts_snac * tts_snac_create_from_gguf(const tts_backend_iface * be, const tts_snac_config * cfg, const tts_gguf * g);
 
 /* ---- Kokoro (kokoro_model::prep_constants / assign_weight, src/models/kokoro/model.cpp:413-930) ---- */
 /* Writes the F32 synthetic model (what tts_kokoro_create fills for cfg with weight_type F32), the input of the

@@ -181,6 +181,9 @@ uint64_t tts_orpheus_weight_bytes(const tts_orpheus * p);
 int32_t tts_orpheus_n_weights(const tts_orpheus * p);
 uint64_t tts_orpheus_weight(tts_orpheus * p, int32_t i, char * name, uint64_t name_cap, int64_t * ne, int32_t * type, void * dst, uint64_t cap);
 tts_tensor * const * tts_orpheus_graph(const tts_orpheus * p, int32_t * n_nodes);
+/* Replaces weight i's bytes (ggml's layout of the type and shape tts_orpheus_weight reports; nbytes must be
+ * that size): a caller's own weights in a runner built for the synthetic ones.  0 on success. */
+int tts_orpheus_set_weight(tts_orpheus * p, int32_t i, const void * src, uint64_t nbytes);
 
 /* Dia-1.6B config (defaults = dia_model, src/models/dia/model.h:62-85; Q8_0 weights for config 4,
  * F32 heads).  Classifier-free guidance runs a (conditioned, unconditioned) pair as the graph batch. */
@@ -231,6 +234,8 @@ uint64_t tts_dia_weight_bytes(const tts_dia * p);
 int32_t tts_dia_n_weights(const tts_dia * p);
 uint64_t tts_dia_weight(tts_dia * p, int32_t i, char * name, uint64_t name_cap, int64_t * ne, int32_t * type, void * dst, uint64_t cap);
 tts_tensor * const * tts_dia_graph(const tts_dia * p, int32_t * n_nodes);
+/* As tts_orpheus_set_weight. */
+int tts_dia_set_weight(tts_dia * p, int32_t i, const void * src, uint64_t nbytes);
 
 /* DAC decoder (codec tokens -> PCM): dac_runner::run / build_dac_graph,
  * /root/reference/src/decoder/dac_model.cpp:139-212.  Defaults = DAC 44.1 kHz as used by

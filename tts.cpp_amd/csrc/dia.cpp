@@ -50,6 +50,7 @@ struct tts_dia {
     tts_sampling samp{};
     int64_t sample_calls = 0;
     std::vector<int32_t> rep_last, rep_count;  // [heads]
+    std::string type_err;  // the first file tensor whose storage type the runner cannot take
 };
 
 extern "C" void tts_dia_set_sampling(tts_dia * p, const tts_sampling * cfg) {
@@ -81,17 +82,47 @@ extern "C" void tts_dia_default_config(tts_dia_config * c) {
     c->arena_bytes = 0;
 }
 
-// kind: 0 = matrix, 1 = norm weight (~1), 3 = embedding
+// The file's name of a runner tensor, after "dia." (assign_to_encoder_layer / assign_to_decoder_layer,
+// model.cpp:59-138; decoder.embeddings.i, :34).
+static std::string dia_file_name(const std::string & name) {
+    static const char * const enc[][2] = {{"q", "q_proj"}, {"k", "k_proj"}, {"v", "v_proj"}, {"o", "o_proj"}, {"self_attn_norm", "pre_sa_norm"},
+                                          {"mlp_norm", "post_sa_norm"}, {"out", "wo"}};
+    static const char * const dec[][2] = {{"self_attn_q", "self_q_proj"}, {"self_attn_k", "self_k_proj"}, {"self_attn_v", "self_v_proj"},
+                                          {"self_attn_o", "self_o_proj"}, {"cross_attn_q", "cross_q_proj"}, {"cross_attn_k", "cross_k_proj"},
+                                          {"cross_attn_v", "cross_v_proj"}, {"cross_attn_o", "cross_o_proj"}, {"self_attn_norm", "pre_sa_norm"},
+                                          {"cross_attn_norm", "pre_ca_norm"}, {"mlp_norm", "pre_mlp_norm"}, {"out", "wo"}};
+    if (name.rfind("decoder.embds.", 0) == 0) return "decoder.embeddings." + name.substr(14);
+    const bool is_enc = name.rfind("encoder.layers.", 0) == 0;
+    if (!is_enc && name.rfind("decoder.layers.", 0) != 0) return name;
+    const size_t dot = name.find('.', 15);
+    if (dot == std::string::npos) return name;
+    const std::string part = name.substr(dot + 1);
+    for (int i = 0; i < (is_enc ? 7 : 12); ++i)
+        if (part == (is_enc ? enc : dec)[i][0]) return name.substr(0, dot + 1) + (is_enc ? enc : dec)[i][1];
+    return name;
+}
+
+// kind: 0 = matrix, 1 = norm weight (~1), 3 = embedding.  With a file attached the tensor takes the file's
+// storage type where the quantize tool's Dia rule (quantize_impl.cpp:42-49) can have put it: F32, F16, Q8_0,
+// Q5_0 or Q4_0 for a matrix, an embedding or a head, F32 for a norm.
 static tts_tensor * wnew(tts_dia * p, int type, int64_t ne0, int64_t ne1, int kind, const std::string & name) {
+    if (p->w.gguf) {
+        type = p->w.file_type(name, TTS_TYPE_F32);
+        const bool ok = type == TTS_TYPE_F32 || (kind != 1 && (type == TTS_TYPE_F16 || type == TTS_TYPE_Q8_0 || type == TTS_TYPE_Q5_0 ||
+                                                               type == TTS_TYPE_Q4_0));
+        if (!ok && p->type_err.empty())
+            p->type_err = "gguf: tensor '" + p->w.gguf_name(name) + "' has type " + std::to_string(type) + ", which a Dia file cannot hold there";
+        if (!ok) type = TTS_TYPE_F32;
+    }
     const weight_fill fill = kind == 1 ? weight_fill::uniform(0.1f, 1.0f) : weight_fill::matrix(kind == 3 ? 0.25f : 0.02f);
     return p->w.add(type, ne0, ne1, 1, name, fill, p->cfg.seed ^ p->w.index());
 }
 
-extern "C" tts_dia * tts_dia_create(const tts_backend_iface * be, const tts_dia_config * cfg) {
-    auto * p = new tts_dia();
-    p->cfg = *cfg;
-    p->be = *be;
+// Declares every weight tensor (the synthetic seeds follow this order); no backend needed.
+static void declare_weights(tts_dia * p) {
     const auto & cf = p->cfg;
+    p->w.prefix = "dia.";
+    p->w.file_name = dia_file_name;
     const int64_t E = cf.encoder_hidden_size, D = cf.decoder_hidden_size, hd = cf.head_size;
     const int64_t EA = (int64_t)cf.encoder_attn_heads * hd, DA = (int64_t)cf.decoder_attn_heads * hd;
     const int64_t DKV = DA / cf.decoder_query_heads;
@@ -135,6 +166,21 @@ extern "C" tts_dia * tts_dia_create(const tts_backend_iface * be, const tts_dia_
     p->dec_norm = wnew(p, TTS_TYPE_F32, D, 1, 1, "decoder.norm");
     for (int i = 0; i < cf.n_output_heads; ++i)
         p->heads.push_back(wnew(p, cf.head_type, D, cf.output_vocab_size, 0, "decoder.heads." + std::to_string(i)));
+}
+
+static tts_dia * dia_create(const tts_backend_iface * be, const tts_dia_config * cfg, const tts_gguf * g) {
+    auto * p = new tts_dia();
+    p->cfg = *cfg;
+    p->be = *be;
+    p->w.attach(g);
+    const auto & cf = p->cfg;
+    const int64_t hd = cf.head_size, DA = (int64_t)cf.decoder_attn_heads * hd;
+    declare_weights(p);
+    if (!p->type_err.empty()) {
+        fprintf(stderr, "%s\n", p->type_err.c_str());
+        tts_dia_free(p);
+        return nullptr;
+    }
     if (!p->w.upload(p->be)) {
         fprintf(stderr, "dia: weight allocation/upload failed\n");
         tts_dia_free(p);
@@ -170,6 +216,8 @@ extern "C" tts_dia * tts_dia_create(const tts_backend_iface * be, const tts_dia_
     }
     return p;
 }
+
+extern "C" tts_dia * tts_dia_create(const tts_backend_iface * be, const tts_dia_config * cfg) { return dia_create(be, cfg, nullptr); }
 
 extern "C" void tts_dia_free(tts_dia * p) {
     if (!p) return;
@@ -514,4 +562,104 @@ extern "C" uint64_t tts_dia_weight(tts_dia * p, int32_t i, char * name, uint64_t
 }
 extern "C" tts_tensor * const * tts_dia_graph(const tts_dia * p, int32_t * n_nodes) {
     return tg::graph_out(p ? &p->gctx : nullptr, n_nodes);
+}
+extern "C" int tts_dia_set_weight(tts_dia * p, int32_t i, const void * src, uint64_t nbytes) {
+    return p && p->w.set(p->be, i, src, (size_t)nbytes) ? TTS_STATUS_SUCCESS : TTS_STATUS_BAD_ARG;
+}
+
+// ---- GGUF loader path (dia_model::prep_constants / assign_weight, model.cpp:3-251) ----
+namespace tts {
+void dac_write_synthetic(const tts_dac_config * cfg, tts_gguf_writer * w);
+}
+
+extern "C" int tts_dia_config_from_gguf(const tts_gguf * g, tts_dia_config * c) {
+    if (!g || !c) return TTS_STATUS_BAD_ARG;
+    const int64_t ak = tts_gguf_find_key(g, "general.architecture");
+    if (ak < 0 || !tts_gguf_get_str(g, ak) || strcmp(tts_gguf_get_str(g, ak), "dia") != 0) {
+        fprintf(stderr, "gguf: not a dia file\n");
+        return TTS_STATUS_BAD_ARG;
+    }
+    gguf_first_u32(g, {"dia.decoder.output_heads"}, &c->n_output_heads);
+    gguf_first_u32(g, {"dia.decoder.layers"}, &c->n_decoder_layers);
+    gguf_first_u32(g, {"dia.encoder.layers"}, &c->n_encoder_layers);
+    gguf_first_u32(g, {"dia.decoder.hidden_size"}, &c->decoder_hidden_size);
+    gguf_first_u32(g, {"dia.decoder.attn_heads"}, &c->decoder_attn_heads);
+    gguf_first_u32(g, {"dia.decoder.query_heads"}, &c->decoder_query_heads);
+    gguf_first_u32(g, {"dia.encoder.attn_heads"}, &c->encoder_attn_heads);
+    gguf_first_u32(g, {"dia.attn_head_size"}, &c->head_size);
+    gguf_first_u32(g, {"dia.encoder.max_context_length"}, &c->max_encoder_context_length);
+    gguf_first_u32(g, {"dia.decoder.output_vocab_size"}, &c->output_vocab_size);
+    gguf_first_u32(g, {"dia.decoder.max_generation_size"}, &c->max_generation_size);
+    const int64_t ck = tts_gguf_find_key(g, "dia.cfg_scale");
+    double scale;
+    if (ck >= 0 && tts_gguf_get_f64(g, ck, &scale)) c->cfg_scale = (float)scale;
+    // the widths no key carries, from the tensors themselves
+    const int64_t E = gguf_tensor_dim(g, "dia.encoder.embedding", 0), ev = gguf_tensor_dim(g, "dia.encoder.embedding", 1);
+    const int64_t ef = gguf_tensor_dim(g, "dia.encoder.layers.0.gate", 1), df = gguf_tensor_dim(g, "dia.decoder.layers.0.gate", 1);
+    const int64_t D = gguf_tensor_dim(g, "dia.decoder.embeddings.0", 0);
+    const int64_t wt = tts_gguf_find_tensor(g, "dia.decoder.layers.0.self_q_proj"), ht = tts_gguf_find_tensor(g, "dia.decoder.heads.0");
+    if (E < 0 || ef < 0 || df < 0 || D < 0 || wt < 0 || ht < 0) {
+        fprintf(stderr, "gguf: dia tensors missing\n");
+        return TTS_STATUS_BAD_ARG;
+    }
+    c->encoder_hidden_size = (int32_t)E;
+    c->encoder_vocab_size = (int32_t)ev;
+    c->encoder_ffn_size = (int32_t)ef;
+    c->decoder_ffn_size = (int32_t)df;
+    c->decoder_hidden_size = (int32_t)D;
+    c->weight_type = tts_gguf_tensor_type(g, wt);
+    c->head_type = tts_gguf_tensor_type(g, ht);
+    if (c->n_output_heads < 1 || c->n_encoder_layers < 0 || c->n_decoder_layers < 1 || c->head_size < 2 || c->decoder_attn_heads < 1 ||
+        c->encoder_attn_heads < 1 || c->decoder_query_heads < 1 || c->decoder_attn_heads % c->decoder_query_heads ||
+        c->max_encoder_context_length < 1 || c->max_generation_size < 1 || c->output_vocab_size < 1) {
+        fprintf(stderr, "gguf: the dia.* keys do not describe a model\n");
+        return TTS_STATUS_BAD_ARG;
+    }
+    return TTS_STATUS_SUCCESS;
+}
+
+extern "C" tts_dia * tts_dia_create_from_gguf(const tts_backend_iface * be, const tts_dia_config * cfg, const tts_gguf * g) {
+    if (!be || !cfg || !g) return nullptr;
+    const int64_t ak = tts_gguf_find_key(g, "general.architecture");
+    if (ak < 0 || !tts_gguf_get_str(g, ak) || strcmp(tts_gguf_get_str(g, ak), "dia") != 0) {
+        fprintf(stderr, "gguf: not a dia file\n");
+        return nullptr;
+    }
+    return dia_create(be, cfg, g);
+}
+
+extern "C" int tts_dia_write_synthetic_gguf(const tts_dia_config * cfg, const tts_dac_config * dac_cfg, const char * path) {
+    if (!cfg || !path) return TTS_STATUS_BAD_ARG;
+    tts_dia p;  // declarations only: no backend, no buffers
+    p.cfg = *cfg;
+    declare_weights(&p);
+    tts_gguf_writer * w = tts_gguf_writer_new();
+    const auto & c = *cfg;
+    // the keys dia_gguf_encoder.py writes (set_gguf_parameters); the token ids and the delay are Dia-1.6B's
+    tts_gguf_set_str(w, "general.architecture", "dia");
+    tts_gguf_set_u32(w, "dia.attn_head_size", (uint32_t)c.head_size);
+    tts_gguf_set_u32(w, "dia.eos_token_id", 1024);
+    tts_gguf_set_u32(w, "dia.bos_token_id", 1026);
+    tts_gguf_set_u32(w, "dia.pad_token_id", 1025);
+    tts_gguf_set_u32(w, "dia.max_delay", 15);
+    tts_gguf_set_u32(w, "dia.encoder.max_context_length", (uint32_t)c.max_encoder_context_length);
+    tts_gguf_set_u32(w, "dia.encoder.attn_heads", (uint32_t)c.encoder_attn_heads);
+    tts_gguf_set_u32(w, "dia.encoder.layers", (uint32_t)c.n_encoder_layers);
+    tts_gguf_set_u32(w, "dia.decoder.hidden_size", (uint32_t)c.decoder_hidden_size);
+    tts_gguf_set_u32(w, "dia.decoder.layers", (uint32_t)c.n_decoder_layers);
+    tts_gguf_set_u32(w, "dia.decoder.output_heads", (uint32_t)c.n_output_heads);
+    tts_gguf_set_u32(w, "dia.decoder.attn_heads", (uint32_t)c.decoder_attn_heads);
+    tts_gguf_set_u32(w, "dia.decoder.query_heads", (uint32_t)c.decoder_query_heads);
+    tts_gguf_set_u32(w, "dia.decoder.output_vocab_size", (uint32_t)c.output_vocab_size);
+    tts_gguf_set_u32(w, "dia.decoder.audio_vocab_size", 1024);
+    tts_gguf_set_u32(w, "dia.decoder.max_generation_size", (uint32_t)c.max_generation_size);
+    // not written by the converter (the reference keeps its default); written only when it is not that default
+    if (c.cfg_scale != 3.0f) tts_gguf_set_f32(w, "dia.cfg_scale", c.cfg_scale);
+    tts_gguf_set_u32(w, "audio.bos_token_id", 1026);  // set_dac_config
+    tts_gguf_set_u32(w, "audio.eos_token_id", 1024);
+    int st = p.w.write(w);
+    if (st == TTS_STATUS_SUCCESS && dac_cfg) dac_write_synthetic(dac_cfg, w);
+    if (st == TTS_STATUS_SUCCESS) st = tts_gguf_writer_write(w, path);
+    tts_gguf_writer_free(w);
+    return st;
 }

@@ -586,7 +586,12 @@ int tts_gguf_tensor_rule(const char * arch_c, const char * name_c, const tts_qua
             }
         }
     } else if (arch == "orpheus") {  // not in the reference (it aborts): every matrix except norms
-        q = ends_with(n, ".weight") && !contains(n, "norm");
+        // a file's names are the checkpoint's without ".weight" (orpheus_gguf_encoder.py:118-122): the projections,
+        // the embedding and the head; norms, layernorms, rope_frequencies and the SNAC decoder stay as they are.
+        // The ".weight" spellings keep the answers they had.
+        q = !starts_with(n, "snac.") && !contains(n, "norm") &&
+            (ends_with(n, ".weight") || n == "orpheus.embed_tokens" || n == "orpheus.lm_head" ||
+             (starts_with(n, "orpheus.layers.") && ends_with(n, "_proj") && (contains(n, ".self_attn.") || contains(n, ".mlp."))));
         if (!p->quantize_output_heads) q = q && !contains(n, "lm_head");
     } else {
         return -1;

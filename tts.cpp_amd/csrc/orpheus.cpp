@@ -49,6 +49,7 @@ struct tts_orpheus {
     tts_sampling samp{};
     int64_t sample_calls = 0;
     std::vector<int32_t> rep_last, rep_count;  // [batch]
+    std::string type_err;  // the first file tensor whose storage type the runner cannot take
 };
 
 extern "C" void tts_orpheus_set_sampling(tts_orpheus * p, const tts_sampling * cfg) {
@@ -97,8 +98,36 @@ static void rope_factors(const tts_orpheus_config & cf, float * out) {
     }
 }
 
-// kind: 0 = matrix, 1 = norm weight (~1), 3 = embedding, 4 = the computed rope factors
+// The file's name of a runner tensor, after "orpheus." (orpheus_model::assign_weight / assign_to_layer,
+// model.cpp:11-61: the converter's names are the checkpoint's without ".weight").
+static std::string orpheus_file_name(const std::string & name) {
+    static const char * const top[][2] = {{"token_embd", "embed_tokens"}, {"output", "lm_head"}, {"output_norm", "norm"}};
+    static const char * const lay[][2] = {{"q", "self_attn.q_proj"}, {"k", "self_attn.k_proj"}, {"v", "self_attn.v_proj"},
+                                          {"o", "self_attn.o_proj"}, {"gate", "mlp.gate_proj"}, {"up", "mlp.up_proj"},
+                                          {"down", "mlp.down_proj"}, {"input_norm", "input_layernorm"},
+                                          {"post_attention_norm", "post_attention_layernorm"}};
+    for (auto & m : top)
+        if (name == m[0]) return m[1];
+    const size_t dot = name.rfind("layers.", 0) == 0 ? name.find('.', 7) : std::string::npos;
+    if (dot == std::string::npos) return name;
+    const std::string part = name.substr(dot + 1);
+    for (auto & m : lay)
+        if (part == m[0]) return name.substr(0, dot + 1) + m[1];
+    return name;
+}
+
+// kind: 0 = matrix, 1 = norm weight (~1), 3 = embedding, 4 = the computed rope factors.  With a file attached
+// a matrix, the embedding and the head each take the type the file gives that tensor (F32, Q4_K, Q8_0, Q5_0 or
+// Q4_0); the norms and the rope factors are F32.
 static tts_tensor * wnew(tts_orpheus * p, int type, int64_t ne0, int64_t ne1, int kind, const std::string & name) {
+    if (p->w.gguf) {
+        type = p->w.file_type(name, TTS_TYPE_F32);
+        const bool quant = type == TTS_TYPE_Q4_K || type == TTS_TYPE_Q8_0 || type == TTS_TYPE_Q5_0 || type == TTS_TYPE_Q4_0;
+        const bool ok = type == TTS_TYPE_F32 || (quant && (kind == 0 || kind == 3));
+        if (!ok && p->type_err.empty())
+            p->type_err = "gguf: tensor '" + p->w.gguf_name(name) + "' has type " + std::to_string(type) + ", which an Orpheus file cannot hold there";
+        if (!ok) type = TTS_TYPE_F32;
+    }
     weight_fill fill = kind == 1 ? weight_fill::uniform(0.1f, 1.0f) : weight_fill::matrix(kind == 3 ? 0.25f : 0.02f);
     if (kind == 4) {
         std::vector<float> f((size_t)ne0);
@@ -108,17 +137,17 @@ static tts_tensor * wnew(tts_orpheus * p, int type, int64_t ne0, int64_t ne1, in
     return p->w.add(type, ne0, ne1, 1, name, fill, p->cfg.seed ^ p->w.index());
 }
 
-extern "C" tts_orpheus * tts_orpheus_create(const tts_backend_iface * be, const tts_orpheus_config * cfg) {
-    auto * p = new tts_orpheus();
-    p->cfg = *cfg;
-    p->be = *be;
-    auto & cf = p->cfg;
-    if (cf.batch < 1) cf.batch = 1;
+static bool config_ok(const tts_orpheus_config & cf) {
+    return cf.n_layers >= 1 && cf.head_size >= 2 && cf.n_attn_heads >= 1 && cf.n_kv_attn_heads >= 1 && cf.vocab_size >= 1 && cf.ffn_size >= 1 &&
+           (int64_t)cf.n_attn_heads * cf.head_size == cf.hidden_size && cf.n_attn_heads % cf.n_kv_attn_heads == 0;
+}
+
+// Declares every weight tensor (the synthetic seeds follow this order); no backend needed.
+static void declare_weights(tts_orpheus * p) {
+    const auto & cf = p->cfg;
+    p->w.prefix = "orpheus.";
+    p->w.file_name = orpheus_file_name;
     const int64_t H = cf.hidden_size, KVH = (int64_t)cf.n_kv_attn_heads * cf.head_size;
-    if ((int64_t)cf.n_attn_heads * cf.head_size != H || cf.n_attn_heads % cf.n_kv_attn_heads) {
-        delete p;
-        return nullptr;
-    }
     p->embd = wnew(p, cf.weight_type, H, cf.vocab_size, 3, "token_embd");
     p->head = wnew(p, cf.weight_type, H, cf.vocab_size, 0, "output");
     p->output_norm = wnew(p, TTS_TYPE_F32, H, 1, 1, "output_norm");
@@ -136,6 +165,26 @@ extern "C" tts_orpheus * tts_orpheus_create(const tts_backend_iface * be, const 
         L.gate = wnew(p, cf.weight_type, H, cf.ffn_size, 0, pre + ".gate");
         L.up = wnew(p, cf.weight_type, H, cf.ffn_size, 0, pre + ".up");
         L.down = wnew(p, cf.weight_type, cf.ffn_size, H, 0, pre + ".down");
+    }
+}
+
+static tts_orpheus * orpheus_create(const tts_backend_iface * be, const tts_orpheus_config * cfg, const tts_gguf * g) {
+    auto * p = new tts_orpheus();
+    p->cfg = *cfg;
+    p->be = *be;
+    p->w.attach(g);
+    auto & cf = p->cfg;
+    if (cf.batch < 1) cf.batch = 1;
+    const int64_t H = cf.hidden_size;
+    if ((int64_t)cf.n_attn_heads * cf.head_size != H || cf.n_attn_heads % cf.n_kv_attn_heads) {
+        delete p;
+        return nullptr;
+    }
+    declare_weights(p);
+    if (!p->type_err.empty()) {
+        fprintf(stderr, "%s\n", p->type_err.c_str());
+        tts_orpheus_free(p);
+        return nullptr;
     }
     if (!p->w.upload(p->be)) {
         fprintf(stderr, "orpheus: weight allocation/upload failed\n");
@@ -171,6 +220,10 @@ extern "C" tts_orpheus * tts_orpheus_create(const tts_backend_iface * be, const 
     }
     tts_orpheus_reset(p);
     return p;
+}
+
+extern "C" tts_orpheus * tts_orpheus_create(const tts_backend_iface * be, const tts_orpheus_config * cfg) {
+    return orpheus_create(be, cfg, nullptr);
 }
 
 extern "C" void tts_orpheus_free(tts_orpheus * p) {
@@ -461,4 +514,74 @@ extern "C" uint64_t tts_orpheus_weight(tts_orpheus * p, int32_t i, char * name, 
 }
 extern "C" tts_tensor * const * tts_orpheus_graph(const tts_orpheus * p, int32_t * n_nodes) {
     return tg::graph_out(p ? &p->gctx : nullptr, n_nodes);
+}
+extern "C" int tts_orpheus_set_weight(tts_orpheus * p, int32_t i, const void * src, uint64_t nbytes) {
+    return p && p->w.set(p->be, i, src, (size_t)nbytes) ? TTS_STATUS_SUCCESS : TTS_STATUS_BAD_ARG;
+}
+
+// ---- GGUF loader path (orpheus_model::prep_constants / prep_layers / assign_weight, model.cpp:11-120) ----
+namespace tts {
+int snac_write_synthetic(const tts_snac_config * cfg, tts_gguf_writer * w);
+}
+
+static bool is_orpheus_file(const tts_gguf * g) {
+    const int64_t ak = tts_gguf_find_key(g, "general.architecture");
+    if (ak >= 0 && tts_gguf_get_str(g, ak) && strcmp(tts_gguf_get_str(g, ak), "orpheus") == 0) return true;
+    fprintf(stderr, "gguf: not an orpheus file\n");
+    return false;
+}
+
+extern "C" int tts_orpheus_config_from_gguf(const tts_gguf * g, tts_orpheus_config * c) {
+    if (!g || !c || !is_orpheus_file(g)) return TTS_STATUS_BAD_ARG;
+    if (!gguf_first_u32(g, {"orpheus.layers"}, &c->n_layers)) {  // prep_layers: the one required key
+        fprintf(stderr, "gguf: key 'orpheus.layers' must be specified\n");
+        return TTS_STATUS_BAD_ARG;
+    }
+    gguf_first_u32(g, {"orpheus.vocab_size"}, &c->vocab_size);
+    gguf_first_u32(g, {"orpheus.attn_heads"}, &c->n_attn_heads);
+    gguf_first_u32(g, {"orpheus.kv_attn_heads"}, &c->n_kv_attn_heads);
+    gguf_first_u32(g, {"orpheus.head_dim"}, &c->head_size);
+    gguf_first_u32(g, {"orpheus.hidden_size"}, &c->hidden_size);
+    const int64_t ffn = gguf_tensor_dim(g, "orpheus.layers.0.mlp.gate_proj", 1);
+    const int64_t wt = tts_gguf_find_tensor(g, "orpheus.layers.0.self_attn.q_proj");
+    if (ffn < 0 || wt < 0) {
+        fprintf(stderr, "gguf: orpheus tensors missing\n");
+        return TTS_STATUS_BAD_ARG;
+    }
+    c->ffn_size = (int32_t)ffn;
+    c->weight_type = tts_gguf_tensor_type(g, wt);
+    if (!config_ok(*c)) {
+        fprintf(stderr, "gguf: the orpheus.* keys do not describe a model\n");
+        return TTS_STATUS_BAD_ARG;
+    }
+    return TTS_STATUS_SUCCESS;
+}
+
+extern "C" tts_orpheus * tts_orpheus_create_from_gguf(const tts_backend_iface * be, const tts_orpheus_config * cfg, const tts_gguf * g) {
+    if (!be || !cfg || !g || !is_orpheus_file(g) || !config_ok(*cfg)) return nullptr;
+    return orpheus_create(be, cfg, g);
+}
+
+extern "C" int tts_orpheus_write_synthetic_gguf(const tts_orpheus_config * cfg, const tts_snac_config * snac_cfg, const char * path) {
+    if (!cfg || !path || !config_ok(*cfg)) return TTS_STATUS_BAD_ARG;
+    tts_orpheus p;  // declarations only: no backend, no buffers
+    p.cfg = *cfg;
+    declare_weights(&p);
+    tts_gguf_writer * w = tts_gguf_writer_new();
+    const auto & c = *cfg;
+    // the keys orpheus_gguf_encoder.py writes (set_gguf_parameters)
+    tts_gguf_set_str(w, "general.architecture", "orpheus");
+    tts_gguf_set_u32(w, "orpheus.stopping_token_id", 128258);
+    tts_gguf_set_u32(w, "orpheus.hidden_size", (uint32_t)c.hidden_size);
+    tts_gguf_set_u32(w, "orpheus.vocab_size", (uint32_t)c.vocab_size);
+    tts_gguf_set_u32(w, "orpheus.attn_heads", (uint32_t)c.n_attn_heads);
+    tts_gguf_set_u32(w, "orpheus.kv_attn_heads", (uint32_t)c.n_kv_attn_heads);
+    tts_gguf_set_u32(w, "orpheus.head_dim", (uint32_t)c.head_size);
+    tts_gguf_set_u32(w, "orpheus.layers", (uint32_t)c.n_layers);
+    tts_gguf_set_u32(w, "orpheus.kv_hidden_size", (uint32_t)(c.hidden_size / (c.n_attn_heads / c.n_kv_attn_heads)));
+    int st = p.w.write(w);
+    if (st == TTS_STATUS_SUCCESS && snac_cfg) st = snac_write_synthetic(snac_cfg, w);
+    if (st == TTS_STATUS_SUCCESS) st = tts_gguf_writer_write(w, path);
+    tts_gguf_writer_free(w);
+    return st;
 }

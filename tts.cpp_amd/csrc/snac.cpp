@@ -72,8 +72,10 @@ extern "C" void tts_snac_default_config(tts_snac_config * c) {
     c->arena_bytes = 0;
 }
 
-static tts_tensor * wnew(tts_snac * d, float scale, float offset, int64_t ne0, int64_t ne1, int64_t ne2, const std::string & name) {
-    return d->w.add(TTS_TYPE_F32, ne0, ne1, ne2, name, weight_fill::uniform(scale, offset), d->cfg.seed ^ d->w.index());
+// in_file = false: a constant the runner builds itself, never in a GGUF file
+static tts_tensor * wnew(tts_snac * d, float scale, float offset, int64_t ne0, int64_t ne1, int64_t ne2, const std::string & name,
+                         bool in_file = true) {
+    return d->w.add(TTS_TYPE_F32, ne0, ne1, ne2, name, weight_fill::uniform(scale, offset), d->cfg.seed ^ d->w.index(), in_file);
 }
 
 // conv kernel [K, IC, OC], uniform +-gain*sqrt(3/fan_in)
@@ -87,12 +89,11 @@ static int64_t snac_hop(const tts_snac_config & c) {
     return hop;
 }
 
-extern "C" tts_snac * tts_snac_create(const tts_backend_iface * be, const tts_snac_config * cfg) {
-    if (!be || !cfg || cfg->n_heads < 1 || cfg->n_heads > 4 || cfg->n_layers < 1 || cfg->n_layers > 8) return nullptr;
-    auto * d = new tts_snac();
-    d->cfg = *cfg;
-    d->be = *be;
+// Declares every weight tensor under the reference's names (snac_model::assign_weight, snac_model.cpp:51-84;
+// general_neural_audio_codec.cpp:36-127); the synthetic seeds follow this order.  No backend needed.
+static void declare_weights(tts_snac * d) {
     const auto & c = d->cfg;
+    d->w.prefix = "snac.";
     for (int i = 0; i < c.n_heads; ++i) {
         snac_quant q;
         const std::string pre = "quantizers." + std::to_string(i);
@@ -135,7 +136,21 @@ extern "C" tts_snac * tts_snac_create(const tts_backend_iface * be, const tts_sn
     d->out_alpha = wnew(d, 0.5f, 1.0f, 1, ch, 1, "alpha_out");
     d->out_kernel = conv_w(d, 7, ch, 1, "final.weight", 0.1f);
     d->out_bias = wnew(d, 0.01f, 0.f, 1, 1, 1, "final.bias");
-    d->one = wnew(d, 0.f, 1.0f, 1, 1, 1, "one");
+    d->one = wnew(d, 0.f, 1.0f, 1, 1, 1, "one", false);
+}
+
+static bool config_ok(const tts_snac_config * cfg) {
+    return cfg && cfg->n_heads >= 1 && cfg->n_heads <= 4 && cfg->n_layers >= 1 && cfg->n_layers <= 8;
+}
+
+static tts_snac * snac_create(const tts_backend_iface * be, const tts_snac_config * cfg, const tts_gguf * g) {
+    if (!be || !config_ok(cfg)) return nullptr;
+    auto * d = new tts_snac();
+    d->cfg = *cfg;
+    d->be = *be;
+    d->w.attach(g);
+    const auto & c = d->cfg;
+    declare_weights(d);
     if (!d->w.upload(d->be)) {
         tts_snac_free(d);
         return nullptr;
@@ -151,6 +166,8 @@ extern "C" tts_snac * tts_snac_create(const tts_backend_iface * be, const tts_sn
     }
     return d;
 }
+
+extern "C" tts_snac * tts_snac_create(const tts_backend_iface * be, const tts_snac_config * cfg) { return snac_create(be, cfg, nullptr); }
 
 extern "C" void tts_snac_free(tts_snac * d) {
     if (!d) return;
@@ -283,3 +300,69 @@ extern "C" uint64_t tts_snac_weight(tts_snac * d, int32_t i, char * name, uint64
 extern "C" uint64_t tts_snac_get_node(tts_snac * d, const char * name, void * dst, uint64_t cap) {
     return d && name ? tg::named_node_out(d->be, d->gctx.nodes, name, dst, cap) : 0;
 }
+
+// ---- GGUF loader path (snac_model::prep_constants / prep_layers / assign_weight, snac_model.cpp:3-84) ----
+extern "C" int tts_snac_config_from_gguf(const tts_gguf * g, tts_snac_config * c) {
+    if (!g || !c) return TTS_STATUS_BAD_ARG;
+    gguf_first_u32(g, {"snac.audio_token_channels"}, &c->n_heads);
+    int n_layers = 0;
+    for (int l = 0; l < 8; ++l) {  // prep_layers: stride, padding and grouping per block
+        const std::string n = std::to_string(l);
+        int32_t s = 0, pd = 0, gr = 0;
+        if (!gguf_first_u32(g, {("snac.snac_layer_stride_" + n).c_str()}, &s)) break;
+        // the reference requires the other two keys; when present they must be what the runner computes
+        if (gguf_first_u32(g, {("snac.snac_layer_padding_" + n).c_str()}, &pd) && (uint32_t)pd != ((uint32_t)s + 1) / 2) {
+            fprintf(stderr, "gguf: SNAC block %d padding %u, the decoder assumes ceil(stride / 2)\n", l, (uint32_t)pd);
+            return TTS_STATUS_UNSUPPORTED;
+        }
+        const int64_t oc = gguf_tensor_dim(g, "snac.layers." + n + ".residual_unit.0.in_weight", 2);
+        if (gguf_first_u32(g, {("snac.snac_layer_grouping_" + n).c_str()}, &gr) && oc >= 0 && gr != oc) {
+            fprintf(stderr, "gguf: SNAC block %d grouping %u, the decoder's residual units are depthwise (%lld)\n", l, (uint32_t)gr, (long long)oc);
+            return TTS_STATUS_UNSUPPORTED;
+        }
+        c->rates[l] = s;
+        n_layers = l + 1;
+    }
+    if (n_layers == 0) {
+        fprintf(stderr, "gguf: key snac.snac_layer_stride_0 must be specified for the SNAC decoder\n");
+        return TTS_STATUS_BAD_ARG;
+    }
+    c->n_layers = n_layers;
+    const char * cbw = "snac.quantizers.0.codebook.weight";
+    const int64_t cd = gguf_tensor_dim(g, cbw, 0), cs = gguf_tensor_dim(g, cbw, 1);
+    const int64_t lat = gguf_tensor_dim(g, "snac.up.weight", 1), dd = gguf_tensor_dim(g, "snac.up.weight", 2);
+    if (cd < 0 || cs < 0 || lat < 0 || dd < 0) {
+        fprintf(stderr, "gguf: SNAC tensors missing\n");
+        return TTS_STATUS_BAD_ARG;
+    }
+    c->codebook_dim = (int32_t)cd;
+    c->codebook_size = (int32_t)cs;
+    c->latent_dim = (int32_t)lat;
+    c->decoder_dim = (int32_t)dd;
+    return config_ok(c) ? TTS_STATUS_SUCCESS : TTS_STATUS_BAD_ARG;
+}
+
+extern "C" tts_snac * tts_snac_create_from_gguf(const tts_backend_iface * be, const tts_snac_config * cfg, const tts_gguf * g) {
+    if (!g) return nullptr;
+    return snac_create(be, cfg, g);
+}
+
+namespace tts {
+// The synthetic SNAC decoder as "snac.*" tensors + snac.* keys (orpheus_gguf_encoder.py:213-221).
+int snac_write_synthetic(const tts_snac_config * cfg, tts_gguf_writer * w) {
+    if (!config_ok(cfg)) return TTS_STATUS_BAD_ARG;
+    tts_snac d;  // declarations only
+    d.cfg = *cfg;
+    declare_weights(&d);
+    tts_gguf_set_u32(w, "snac.audio_token_channels", (uint32_t)cfg->n_heads);
+    int ch = cfg->decoder_dim;
+    for (int l = 0; l < cfg->n_layers; ++l) {
+        ch /= 2;
+        const std::string n = std::to_string(l);
+        tts_gguf_set_u32(w, ("snac.snac_layer_stride_" + n).c_str(), (uint32_t)cfg->rates[l]);
+        tts_gguf_set_u32(w, ("snac.snac_layer_padding_" + n).c_str(), (uint32_t)((cfg->rates[l] + 1) / 2));
+        tts_gguf_set_u32(w, ("snac.snac_layer_grouping_" + n).c_str(), (uint32_t)ch);
+    }
+    return d.w.write(w);
+}
+}  // namespace tts

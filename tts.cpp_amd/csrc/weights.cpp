@@ -103,6 +103,12 @@ bool weight_store::upload(const tts_backend_iface & be) {
     return true;
 }
 
+bool weight_store::set(const tts_backend_iface & be, int32_t i, const void * src, size_t nbytes) {
+    tts_tensor * t = i >= 0 && i < size() ? specs[(size_t)i].t : nullptr;
+    if (!t || !t->data || !src || nbytes != tg::nbytes(t)) return false;
+    return be.set_tensor(be.ctx, t, src) == 0;
+}
+
 int weight_store::write(tts_gguf_writer * w) const {
     std::vector<char> host;
     for (auto & s : specs) {

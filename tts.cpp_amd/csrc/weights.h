@@ -62,6 +62,8 @@ struct weight_store {
     // hold -- a missing tensor, another type or another element layout fails with the reason on stderr --
     // and the synthetic bytes otherwise.  Detaches the file.
     bool upload(const tts_backend_iface & be);
+    // Replaces tensor i's bytes after upload (the type and shape it was declared with, nbytes of ggml's layout).
+    bool set(const tts_backend_iface & be, int32_t i, const void * src, size_t nbytes);
     // Every file-backed tensor's synthetic bytes into w, trailing 1-sized dimensions dropped.
     int write(tts_gguf_writer * w) const;
     void release(const tts_backend_iface & be);

@@ -531,6 +531,16 @@ def lib():
         "tts_parler_write_synthetic_gguf": (ctypes.c_int, [ctypes.POINTER(ParlerConfig), ctypes.POINTER(DacConfig), ctypes.c_char_p]),
         "tts_dac_config_from_gguf": (ctypes.c_int, [vp, ctypes.POINTER(DacConfig)]),
         "tts_dac_create_from_gguf": (vp, [ctypes.POINTER(BackendIface), ctypes.POINTER(DacConfig), vp]),
+        "tts_dia_config_from_gguf": (ctypes.c_int, [vp, ctypes.POINTER(DiaConfig)]),
+        "tts_dia_create_from_gguf": (vp, [ctypes.POINTER(BackendIface), ctypes.POINTER(DiaConfig), vp]),
+        "tts_dia_write_synthetic_gguf": (ctypes.c_int, [ctypes.POINTER(DiaConfig), ctypes.POINTER(DacConfig), ctypes.c_char_p]),
+        "tts_dia_set_weight": (ctypes.c_int, [vp, i32, vp, u64]),
+        "tts_orpheus_config_from_gguf": (ctypes.c_int, [vp, ctypes.POINTER(OrpheusConfig)]),
+        "tts_orpheus_create_from_gguf": (vp, [ctypes.POINTER(BackendIface), ctypes.POINTER(OrpheusConfig), vp]),
+        "tts_orpheus_write_synthetic_gguf": (ctypes.c_int, [ctypes.POINTER(OrpheusConfig), ctypes.POINTER(SnacConfig), ctypes.c_char_p]),
+        "tts_orpheus_set_weight": (ctypes.c_int, [vp, i32, vp, u64]),
+        "tts_snac_config_from_gguf": (ctypes.c_int, [vp, ctypes.POINTER(SnacConfig)]),
+        "tts_snac_create_from_gguf": (vp, [ctypes.POINTER(BackendIface), ctypes.POINTER(SnacConfig), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -718,6 +728,14 @@ class _Runner:
             out[name.value.decode()] = (ty.value, tuple(ne), a)
         return out
 
+    def set_weight(self, i, data):
+        """Replaces weight i's stored bytes (tts_<PREFIX>_set_weight: Dia and Orpheus); data: the uint8 bytes of
+        the type and shape weights_raw() reports for it."""
+        import numpy as np
+        d = np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+        if self._fn("set_weight")(self.ptr, i, d.ctypes.data, d.nbytes) != 0:
+            raise RuntimeError(f"setting weight {i} failed ({d.nbytes} bytes)")
+
     def plan_stats(self, mask=None):
         """Fusion coverage of the last graph (no device needed): {item kind: count, "unfused": n}."""
         n = ctypes.c_int32()
@@ -784,13 +802,22 @@ class Dia(_Runner):
     """Dia-1.6B runner (encoder step + CFG decoder steps) over a backend vtable."""
     PREFIX = "tts_dia"
 
-    def __init__(self, iface, cfg):
+    def __init__(self, iface, cfg, gguf=None):
+        """gguf: a Gguf file whose "dia.*" tensors are the weights (cfg from dia_config_from_gguf)."""
         self.L = lib()
         self.cfg = cfg
         self._iface = iface
-        self.ptr = self.L.tts_dia_create(ctypes.byref(iface), ctypes.byref(cfg))
+        if gguf is None:
+            self.ptr = self.L.tts_dia_create(ctypes.byref(iface), ctypes.byref(cfg))
+        else:
+            self.ptr = self.L.tts_dia_create_from_gguf(ctypes.byref(iface), ctypes.byref(cfg), gguf.ptr)
         if not self.ptr:
             raise RuntimeError("tts_dia_create failed")
+
+    @classmethod
+    def from_gguf(cls, iface, g, **kw):
+        """A runner over the Gguf file g; kw overrides config fields the file does not carry (seed, arena_bytes)."""
+        return cls(iface, dia_config_from_gguf(g, **kw), gguf=g)
 
     def prefill(self, text_ids, audio):
         """text_ids: byte tokens of the conditioned prompt (the unconditioned row is all padding 0)."""
@@ -893,13 +920,22 @@ class Orpheus(_Runner):
     """Orpheus-3B decoder runner over a backend vtable (HIP, or the oracle in tests)."""
     PREFIX = "tts_orpheus"
 
-    def __init__(self, iface, cfg):
+    def __init__(self, iface, cfg, gguf=None):
+        """gguf: a Gguf file whose "orpheus.*" tensors are the weights (cfg from orpheus_config_from_gguf)."""
         self.L = lib()
         self.cfg = cfg
         self._iface = iface
-        self.ptr = self.L.tts_orpheus_create(ctypes.byref(iface), ctypes.byref(cfg))
+        if gguf is None:
+            self.ptr = self.L.tts_orpheus_create(ctypes.byref(iface), ctypes.byref(cfg))
+        else:
+            self.ptr = self.L.tts_orpheus_create_from_gguf(ctypes.byref(iface), ctypes.byref(cfg), gguf.ptr)
         if not self.ptr:
             raise RuntimeError("tts_orpheus_create failed")
+
+    @classmethod
+    def from_gguf(cls, iface, g, **kw):
+        """A runner over the Gguf file g; kw = the fields the file does not carry (batch, max_ctx, seed, arena_bytes)."""
+        return cls(iface, orpheus_config_from_gguf(g, **kw), gguf=g)
 
     def prefill(self, tokens, want_logits=True):
         import numpy as np
@@ -1129,13 +1165,22 @@ class Snac(_Runner):
     PREFIX = "tts_snac"
     TYPED_WEIGHTS = False
 
-    def __init__(self, iface, cfg):
+    def __init__(self, iface, cfg, gguf=None):
+        """gguf: a Gguf file whose "snac.*" tensors are the weights (cfg from snac_config_from_gguf)."""
         self.L = lib()
         self.cfg = cfg
         self._iface = iface
-        self.ptr = self.L.tts_snac_create(ctypes.byref(iface), ctypes.byref(cfg))
+        if gguf is None:
+            self.ptr = self.L.tts_snac_create(ctypes.byref(iface), ctypes.byref(cfg))
+        else:
+            self.ptr = self.L.tts_snac_create_from_gguf(ctypes.byref(iface), ctypes.byref(cfg), gguf.ptr)
         if not self.ptr:
             raise RuntimeError("tts_snac_create failed")
+
+    @classmethod
+    def from_gguf(cls, iface, g, **kw):
+        """A decoder over the Gguf file g; kw = the fields the file does not carry (max_frames, repeats, arena_bytes)."""
+        return cls(iface, snac_config_from_gguf(g, **kw), gguf=g)
 
     @property
     def hop(self):
@@ -1568,6 +1613,52 @@ def dac_config_from_gguf(g, **kw):
     if lib().tts_dac_config_from_gguf(g.ptr, ctypes.byref(cfg)) != 0:
         raise RuntimeError("no usable DAC decoder in the GGUF file")
     return cfg
+
+
+def _config_from_gguf(make, fn, what, g, kw):
+    cfg = make(**kw)
+    if fn(g.ptr, ctypes.byref(cfg)) != 0:
+        raise RuntimeError(f"not a usable {what} GGUF file")
+    if kw:  # the caller's keywords win over what the file says, set the way `make` sets them
+        over = make(**kw)
+        for k in kw:
+            v = getattr(over, k)
+            if isinstance(v, ctypes.Array):
+                for i, x in enumerate(v):
+                    getattr(cfg, k)[i] = x
+            else:
+                setattr(cfg, k, v)
+    return cfg
+
+
+def dia_config_from_gguf(g, **kw):
+    """The model fields from the file's dia.* keys and tensor shapes; kw = seed, arena_bytes (or overrides)."""
+    return _config_from_gguf(dia_config, lib().tts_dia_config_from_gguf, "dia", g, kw)
+
+
+def orpheus_config_from_gguf(g, **kw):
+    """The model fields from the file's orpheus.* keys and tensor shapes; kw = batch, max_ctx, seed, arena_bytes."""
+    return _config_from_gguf(orpheus_config, lib().tts_orpheus_config_from_gguf, "orpheus", g, kw)
+
+
+def snac_config_from_gguf(g, **kw):
+    """The SNAC decoder's fields from the file's snac.* keys and tensor shapes; kw = max_frames, repeats, arena_bytes."""
+    return _config_from_gguf(snac_config, lib().tts_snac_config_from_gguf, "snac", g, kw)
+
+
+def write_dia_synthetic_gguf(path, cfg, dac_cfg=None):
+    """The Dia runner's synthetic weights for cfg (and a DAC decoder) as a GGUF file with the reference's names and keys."""
+    st = lib().tts_dia_write_synthetic_gguf(ctypes.byref(cfg), ctypes.byref(dac_cfg) if dac_cfg is not None else None, str(path).encode())
+    if st != 0:
+        raise RuntimeError(f"writing {path} failed {st}")
+
+
+def write_orpheus_synthetic_gguf(path, cfg, snac_cfg=None):
+    """The Orpheus runner's synthetic weights for cfg (and a SNAC decoder) as a GGUF file with the reference's names and keys."""
+    st = lib().tts_orpheus_write_synthetic_gguf(ctypes.byref(cfg), ctypes.byref(snac_cfg) if snac_cfg is not None else None,
+                                                str(path).encode())
+    if st != 0:
+        raise RuntimeError(f"writing {path} failed {st}")
 
 
 def write_parler_synthetic_gguf(path, cfg, dac_cfg=None):

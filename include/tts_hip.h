@@ -374,6 +374,17 @@ enum tts_hip_option {
                                       (k_gemm_q4_0 / k_gemm_q4_0s, bit-identical); 0 = one GEMV launch per 8 columns */
     TTS_HIP_OPT_GEMM_Q4_0_STAGED = 52, /* many-column Q4_0 GEMM with K % 256 == 0: 2 (default) = staged kernel over 64 x 128
                                       output tiles, 1 = over 64 x 64 tiles, 0 = the direct-load kernel */
+    TTS_HIP_OPT_CONV_VFMA = 53,   /* fused conv_1d on f64 vector FMAs (k_conv1d_f64v: lane = output position, one output channel
+                                     per workgroup row, one f64 accumulator per output taking its terms in the oracle's order
+                                     r = ic * K + k: the oracle's bits).  It applies to stride-1 convs that the launcher does not
+                                     split over input channels and whose window of 1024 + (K - 1) d positions is at most 4096.
+                                     0 = never; 1 (default) = where measured faster: convs of fewer than 8 output channels (the DAC
+                                     output conv, which fills one row of a 16-row MFMA tile) -- a rule of the shape alone, so a
+                                     captured graph stays valid; 2 = wherever it applies (tests).  The environment variable
+                                     TTS_HIP_OPT_CONV_VFMA sets the default */
+    TTS_HIP_OPT_CONV_TILE96 = 54, /* 1 (default) = unsplit fused conv_1d launches whose OC is a multiple of 96 (every DAC-44k decoder
+                                     width) run 96-row workgroup tiles (four waves of 48 x 32) instead of 64-row ones; each output's
+                                     MFMAs are the same in the same order: bit-identical.  0 = 64-row tiles */
     TTS_HIP_OPT_COALESCE = 37,    /* 1 (default): while the process-wide coalescer is on (tts_hip_coalesce_enable), this
                                      backend's graph_compute of a one-prompt decode step may join the same step of other
                                      backends on the device as one coalesced launch (tts_hip_coalesce_stats); 0 = never */

@@ -94,6 +94,8 @@ case "$1" in
     hipcc --offload-arch=gfx950 -O3 scripts/microbench_sync.hip -o build/microbench_sync && timeout -k 10 120 build/microbench_sync > "$O/sync.jsonl" 2>&1 && cat "$O/sync.jsonl" ;;
   mfma_f64)    # the f64 MFMA ceiling
     hipcc --offload-arch=gfx950 -O3 scripts/mfma_f64_peak.hip -o build/mfma_f64_peak && timeout -k 10 120 build/mfma_f64_peak > "$O/mfma_f64.log" 2>&1 && cat "$O/mfma_f64.log" ;;
+  fma_f64)     # the f64 vector-FMA rate beside the MFMA's, and both engines at once
+    hipcc --offload-arch=gfx950 -O3 scripts/fma_f64_peak.hip -o build/fma_f64_peak && timeout -k 10 120 build/fma_f64_peak > "$O/fma_f64.log" 2>&1 && cat "$O/fma_f64.log" ;;
   *)
-    echo "usage: $0 {ar|ar_trace|orph_trace|dia|dia_trace|dac20_trace|replicas|cu_partition|kernarg|gemv_phase|attn|dac|dac_short|tests|sync|mfma_f64} [args]"; exit 2 ;;
+    echo "usage: $0 {ar|ar_trace|orph_trace|dia|dia_trace|dac20_trace|replicas|cu_partition|kernarg|gemv_phase|attn|dac|dac_short|tests|sync|mfma_f64|fma_f64} [args]"; exit 2 ;;
 esac

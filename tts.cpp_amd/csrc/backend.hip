@@ -116,6 +116,8 @@ tts_hip_backend_t tts_hip_backend_init(int device) {
     TTS_HIP_CHECK(hipMalloc((void **)&be->vec_scratch, kVecScratchFloats * sizeof(float)));
     be->conv_stage_floats = (size_t)8 << 20;  // 32 MiB: a [T, C] conv output of the largest vocoder level
     TTS_HIP_CHECK(hipMalloc((void **)&be->conv_stage, be->conv_stage_floats * sizeof(float)));
+    if (const char * e = getenv("TTS_HIP_OPT_CONV_VFMA"))  // the option's default
+        if (e[0] >= '0' && e[0] <= '2' && !e[1]) be->conv_vfma = e[0] - '0';
     be->conv_part_doubles = (size_t)8 << 20;  // 64 MiB of f64 partial sums
     TTS_HIP_CHECK(hipMalloc((void **)&be->conv_part, be->conv_part_doubles * sizeof(double)));
     be->lstm_floats = kLstmFloats;
@@ -767,6 +769,8 @@ extern "C" int tts_hip_set_option(tts_hip_backend_t be, int option, int value) {
         case TTS_HIP_OPT_FUSION: be->fusion = value; return 0;
         case TTS_HIP_OPT_CONVT_LDS: be->convt_lds = value != 0; return 0;
         case TTS_HIP_OPT_CONV_SPLIT: be->conv_split = value < 0 ? 1 : value; return 0;
+        case TTS_HIP_OPT_CONV_VFMA: be->conv_vfma = value < 0 || value > 2 ? 1 : value; return 0;
+        case TTS_HIP_OPT_CONV_TILE96: be->conv_tile96 = value != 0; return 0;
         case TTS_HIP_OPT_PROFILE_GEMV: be->profile_gemv = value != 0; return 0;
         case TTS_HIP_OPT_GRAPHS: be->use_graphs = value != 0; return 0;
         case TTS_HIP_OPT_CONV_F32ACC:

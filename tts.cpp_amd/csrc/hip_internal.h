@@ -535,6 +535,8 @@ struct tts_hip_backend {
     // tiles alone would leave most CUs idle), summed in split order by a second pass
     double * conv_part = nullptr;
     size_t conv_part_doubles = 0;
+    int conv_vfma = 1;   // TTS_HIP_OPT_CONV_VFMA: 0 = never, 1 = convs of fewer than 8 output channels, 2 = wherever it applies
+    int conv_tile96 = 1;  // TTS_HIP_OPT_CONV_TILE96: the 96-row tile of the fused conv_1d when OC % 96 == 0
     int conv_split = 1;  // TTS_HIP_OPT_CONV_SPLIT: 1 = split short convolutions to ~512 workgroups, N > 1 = to ~N, 0 = never
     int fusion = 0x3FFF;  // bitmask of TTS_FUSE_* patterns (all on)
     bool profile_gemv = false;

@@ -298,20 +298,36 @@ bool launch_gemm_f16(tts_hip_backend * be, const tts_tensor * node) {
 // 32-wide reduction batch is one MFMA into a zeroed f32 accumulator -- its products are exact and
 // only the 32-term sum rounds -- and the batch result is added to the f64 accumulator, so the
 // rounding stays per 32 terms instead of compounding over the whole K (TTS_HIP_OPT_CONV_F32ACC 2).
+// MT: 16-row MFMA tiles per wave.  2 = the 64-channel workgroup tile above; 3 = a 96-channel tile (4 waves
+// of 48 x 32, acc[3][2]; 254 registers, so the two waves per SIMD of MT = 2 are asked for explicitly) for
+// channel counts that are multiples of 96 (every DAC-44k decoder width), where 64-row tiles leave half of
+// every second workgroup's waves without rows.  An output's MFMAs run over the same r in the same order
+// under either tile, so the result does not depend on MT.
 typedef _Float16 h16x8_t __attribute__((ext_vector_type(8)));
-template <bool W16, bool BIAS, bool RES, bool H32 = false>
-__global__ __launch_bounds__(256) void k_conv1d_f64(Conv1dArgs a) {
+
+// The epilogue of one output, shared with k_conv1d_f64v: (float)acc, + bias, residual +, each an f32 rounding.
+template <bool BIAS, bool RES>
+__device__ __forceinline__ float conv1d_epilogue(double acc, float bias, float res) {
+    float v = (float)acc;
+    if (BIAS) v = v + bias;
+    if (RES) v = res + v;
+    return v;
+}
+
+template <bool W16, bool BIAS, bool RES, bool H32 = false, int MT = 2>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 1 : 2))) void k_conv1d_f64(Conv1dArgs a) {
+    constexpr int OCT = 32 * MT, WN = CONV1D_WN * MT / 2;  // workgroup rows, staged kernel elements per thread
     extern __shared__ float sm[];
     __shared__ int xoff[CONV1D_MAX_R];  // r -> x-window slot (ic*xw + k*d), zero slot past R
     __shared__ int wofs[CONV1D_MAX_R];  // r -> kernel element offset (k*wk + ic*wic), -1 past R
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c16 = lane & 15, kq = lane >> 4;
     const int64_t ol0 = (int64_t)blockIdx.x * 64;
-    const int oc0 = blockIdx.y * 64;
+    const int oc0 = blockIdx.y * OCT;
     const int K = a.K, s = a.s, icc = a.icc, xw = a.xw, rs = a.rs;
     const int R = icc * K, Rp = (R + 31) & ~31;  // reduction padded to whole MFMA batches
     float * xs = sm;                 // [icc][xw] + 1 zero slot
-    float * ws = sm + icc * xw + 1;  // [64 oc][rs]
+    float * ws = sm + icc * xw + 1;  // [OCT oc][rs]
     const int zslot = icc * xw;
     for (int r = threadIdx.x; r < Rp; r += 256) {
         const int ic = r / K, k = r - ic * K;
@@ -320,22 +336,26 @@ __global__ __launch_bounds__(256) void k_conv1d_f64(Conv1dArgs a) {
     }
     if (threadIdx.x == 0) xs[zslot] = 0.f;
     __syncthreads();
-    const int wr0 = (wave >> 1) * 32, wc0 = (wave & 1) * 32;  // wave's oc / ol offsets in the tile
+    const int wr0 = (wave >> 1) * 16 * MT, wc0 = (wave & 1) * 32;  // wave's oc / ol offsets in the tile
     const bool wave_live = oc0 + wr0 < a.OC && ol0 + wc0 < a.OL;  // wave-uniform
-    f64x4_t acc[2][2] = {};
+    f64x4_t acc[MT][2] = {};
     const int64_t base = ol0 * s - a.p;
     // Staging: thread t owns x-window elements e = t + 256u (u < CONV1D_XN) and kernel-slice
     // elements t + 256u (u < CONV1D_WN); their byte offsets relative to the chunk's first channel
     // are fixed for the whole kernel and computed once.  Loads go through buffer descriptors (an
     // out-of-range offset -- padding, the channel tail -- reads 0) into registers one chunk
     // ahead, so the next chunk's loads are in flight while the current one computes.
-    const int EX = icc * xw, EW = 64 * Rp;
+    const int EX = icc * xw, EW = OCT * Rp;
     constexpr int esz = W16 ? 2 : 4;
     const uint32_t OOB = 0x80000000u;
     const auto xr = __builtin_amdgcn_make_buffer_rsrc(a.x.data, 0, a.x_bytes, 0x00020000);
     const auto wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.w), 0, a.w_bytes, 0x00020000);
-    uint32_t xrel[CONV1D_XN], wrel[CONV1D_WN];
-    int xic[CONV1D_XN], wic[CONV1D_WN];  // channel within the chunk (for the tail chunk), -1 = unused
+    // Rp is 32 or 64 (conv1d_icc), so element e of the kernel slice is row e >> rsh, tap r = e & (Rp - 1),
+    // and sits at ws[e + (e >> rsh)] (rs = Rp + 1).  Channel c of the chunk holds the x elements
+    // [c * xw, (c + 1) * xw) and the taps [c * K, (c + 1) * K): the tail chunk's missing channels are
+    // the elements past nic * xw and the taps past nic * K.
+    const int rsh = Rp == 64 ? 6 : 5;
+    uint32_t xrel[CONV1D_XN], wrel[WN];
 #pragma unroll
     for (int u = 0; u < CONV1D_XN; ++u) {
         const int e = (int)threadIdx.x + 256 * u;
@@ -343,30 +363,28 @@ __global__ __launch_bounds__(256) void k_conv1d_f64(Conv1dArgs a) {
         const int64_t pos = base + q;
         const bool ok = e < EX && pos >= 0 && pos < a.L;
         xrel[u] = ok ? (uint32_t)(pos * a.x.nb[0] + (int64_t)ic * a.x.nb[1]) : OOB;
-        xic[u] = e < EX ? ic : -1;
     }
 #pragma unroll
-    for (int u = 0; u < CONV1D_WN; ++u) {
+    for (int u = 0; u < WN; ++u) {
         const int e = (int)threadIdx.x + 256 * u;
-        const int oc = e / Rp, r = e - oc * Rp;
+        const int oc = e >> rsh, r = e & (Rp - 1);
         const int wo = e < EW ? wofs[r] : -1;
         const bool ok = wo >= 0 && oc0 + oc < a.OC;
         wrel[u] = ok ? (uint32_t)(((int64_t)(oc0 + oc) * a.woc + wo) * esz) : OOB;
-        wic[u] = e < EW ? (r < R ? r / K : icc) : -1;
     }
-    float xv[CONV1D_XN], wv[CONV1D_WN];
+    float xv[CONV1D_XN], wv[WN];
     auto fetch = [&](int ic0) {
         const int nic = min(icc, (int)(a.IC - ic0));
         const uint32_t xc = (uint32_t)((int64_t)ic0 * a.x.nb[1]);
         const uint32_t wc = (uint32_t)((int64_t)ic0 * a.wic * esz);
 #pragma unroll
         for (int u = 0; u < CONV1D_XN; ++u) {
-            const uint32_t off = (xrel[u] == OOB || xic[u] >= nic) ? OOB : xrel[u] + xc;
+            const uint32_t off = (xrel[u] == OOB || (int)threadIdx.x + 256 * u >= nic * xw) ? OOB : xrel[u] + xc;
             xv[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, off, 0, 0));
         }
 #pragma unroll
-        for (int u = 0; u < CONV1D_WN; ++u) {
-            const uint32_t off = (wrel[u] == OOB || wic[u] >= nic) ? OOB : wrel[u] + wc;
+        for (int u = 0; u < WN; ++u) {
+            const uint32_t off = (wrel[u] == OOB || (((int)threadIdx.x + 256 * u) & (Rp - 1)) >= nic * K) ? OOB : wrel[u] + wc;
             if (W16) wv[u] = __half2float(__builtin_bit_cast(__half, __builtin_amdgcn_raw_buffer_load_b16(wr, off, 0, 0)));
             else wv[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wr, off, 0, 0));
         }
@@ -379,14 +397,12 @@ __global__ __launch_bounds__(256) void k_conv1d_f64(Conv1dArgs a) {
         // f16 rounding (im2col's dst type / MUL_MAT's vec_dot_type) on the way into LDS
 #pragma unroll
         for (int u = 0; u < CONV1D_XN; ++u)
-            if (xic[u] >= 0) xs[(int)threadIdx.x + 256 * u] = __half2float(__float2half_rn(xv[u]));
+            if ((int)threadIdx.x + 256 * u < EX) xs[(int)threadIdx.x + 256 * u] = __half2float(__float2half_rn(xv[u]));
 #pragma unroll
-        for (int u = 0; u < CONV1D_WN; ++u)
-            if (wic[u] >= 0) {
-                const int e = (int)threadIdx.x + 256 * u;
-                const int oc = e / Rp;
-                ws[oc * rs + (e - oc * Rp)] = W16 ? wv[u] : __half2float(__float2half_rn(wv[u]));
-            }
+        for (int u = 0; u < WN; ++u) {
+            const int e = (int)threadIdx.x + 256 * u;
+            if (e < EW) ws[e + (e >> rsh)] = W16 ? wv[u] : __half2float(__float2half_rn(wv[u]));
+        }
         __syncthreads();
         if (ic0 + icc < ic_hi) fetch(ic0 + icc);
         // a wave whose 32 x 32 sub-tile lies wholly past the last output channel or position (OC = 96
@@ -404,17 +420,17 @@ __global__ __launch_bounds__(256) void k_conv1d_f64(Conv1dArgs a) {
                 int xo[8];
 #pragma unroll
                 for (int u = 0; u < 8; ++u) xo[u] = xoff[r0 + 8 * kq + u];
-                h16x8_t A[2], B[2];
+                h16x8_t A[MT], B[2];
 #pragma unroll
-                for (int t = 0; t < 2; ++t)
+                for (int u = 0; u < 8; ++u) {
+                    const bool z = xo[u] == zslot;
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const bool z = xo[u] == zslot;
-                        A[t][u] = (_Float16)ws[(wr0 + 16 * t + c16) * rs + r0 + 8 * kq + u];  // f16-rounded: exact
-                        B[t][u] = (_Float16)xs[z ? zslot : xo[u] + (wc0 + 16 * t + c16) * s];
-                    }
+                    for (int t = 0; t < MT; ++t) A[t][u] = (_Float16)ws[(wr0 + 16 * t + c16) * rs + r0 + 8 * kq + u];  // f16-rounded: exact
 #pragma unroll
-                for (int ti = 0; ti < 2; ++ti)
+                    for (int t = 0; t < 2; ++t) B[t][u] = (_Float16)xs[z ? zslot : xo[u] + (wc0 + 16 * t + c16) * s];
+                }
+#pragma unroll
+                for (int ti = 0; ti < MT; ++ti)
 #pragma unroll
                     for (int tj = 0; tj < 2; ++tj) {
                         const f32x4 pr = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[ti], B[tj], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
@@ -427,21 +443,20 @@ __global__ __launch_bounds__(256) void k_conv1d_f64(Conv1dArgs a) {
             int xo[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) xo[u] = xoff[r0 + 4 * u + kq];
-            float af[8][2], bf[8][2];
+            float af[8][MT], bf[8][2];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int r = r0 + 4 * u + kq;
                 const bool z = xo[u] == zslot;
 #pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    af[u][t] = ws[(wr0 + 16 * t + c16) * rs + r];
-                    bf[u][t] = xs[z ? zslot : xo[u] + (wc0 + 16 * t + c16) * s];
-                }
+                for (int t = 0; t < MT; ++t) af[u][t] = ws[(wr0 + 16 * t + c16) * rs + r];
+#pragma unroll
+                for (int t = 0; t < 2; ++t) bf[u][t] = xs[z ? zslot : xo[u] + (wc0 + 16 * t + c16) * s];
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u)
 #pragma unroll
-                for (int ti = 0; ti < 2; ++ti)
+                for (int ti = 0; ti < MT; ++ti)
 #pragma unroll
                     for (int tj = 0; tj < 2; ++tj)
                         acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)af[u][ti], (double)bf[u][tj], acc[ti][tj], 0, 0, 0);
@@ -454,7 +469,7 @@ __global__ __launch_bounds__(256) void k_conv1d_f64(Conv1dArgs a) {
             const int64_t ol = ol0 + wc0 + 16 * tj + c16;
             if (ol >= a.OL) continue;
 #pragma unroll
-            for (int ti = 0; ti < 2; ++ti)
+            for (int ti = 0; ti < MT; ++ti)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int oc = oc0 + wr0 + 16 * ti + (H32 ? 4 * kq + e : kq + 4 * e);
@@ -464,9 +479,9 @@ __global__ __launch_bounds__(256) void k_conv1d_f64(Conv1dArgs a) {
         return;
     }
     // epilogue: bias and residual operands fetched for all 32 outputs first (clamped, branchless)
-    float bv[2][4], rv[2][2][4];
+    float bv[MT][4], rv[2][MT][4];
 #pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
+    for (int ti = 0; ti < MT; ++ti)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             // accumulator row of register e: f64 MFMA (lane >> 4) + 4e, f32 MFMA 4 (lane >> 4) + e
@@ -483,17 +498,109 @@ __global__ __launch_bounds__(256) void k_conv1d_f64(Conv1dArgs a) {
         const int64_t ol = ol0 + wc0 + 16 * tj + c16;
         if (ol >= a.OL) continue;
 #pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
+        for (int ti = 0; ti < MT; ++ti)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int oc = oc0 + wr0 + 16 * ti + (H32 ? 4 * kq + e : kq + 4 * e);
                 if (oc >= a.OC) continue;
-                float v = (float)acc[ti][tj][e];
-                if (BIAS) v = v + bv[ti][e];
-                if (RES) v = rv[tj][ti][e] + v;
-                a.y[ol + (int64_t)oc * a.ycs] = v;
+                a.y[ol + (int64_t)oc * a.ycs] = conv1d_epilogue<BIAS, RES>(acc[ti][tj][e], bv[ti][e], rv[tj][ti][e]);
             }
     }
+}
+
+// conv_1d (s = 1) on f64 vector FMAs for convs of very few output channels (the DAC output conv, OC = 1,
+// fills one row of a 16-row MFMA tile).  Lane = output position: a workgroup owns one output channel
+// (blockIdx.y) x 256 * NP positions, thread t the positions ol0 + t + 256 j.  Per chunk of icc input
+// channels the x window (256 * NP + (K - 1) d positions) and the channel's kernel slice are staged in LDS
+// as f16-rounded doubles, so the loop is one broadcast kernel read, NP x reads and NP v_fma_f64 per term.
+// Every output has ONE accumulator and takes its terms in r = ic * K + k ascending, the oracle's order
+// (ggml_vec_dot_f16: exact f16 x f16 products summed into one f64), so the f32 result is the oracle's bit
+// for bit.  Loads go through buffer descriptors one chunk ahead, as in k_conv1d_f64.
+constexpr int CONV1DV_NP = 4;
+template <bool W16, bool BIAS, bool RES>
+__global__ __launch_bounds__(256) void k_conv1d_f64v(Conv1dArgs a) {
+    constexpr int NP = CONV1DV_NP;
+    extern __shared__ double smd[];
+    const int K = a.K, d = a.d, icc = a.icc, xw = a.xw, R = icc * K;
+    double * xs = smd;             // [icc][xw]
+    double * ws = smd + icc * xw;  // [icc * K]
+    const int tid = threadIdx.x;
+    const int64_t ol0 = (int64_t)blockIdx.x * (256 * NP);
+    const int oc = blockIdx.y;
+    const int64_t base = ol0 - a.p;
+    const int EX = icc * xw;
+    constexpr int esz = W16 ? 2 : 4;
+    const uint32_t OOB = 0x80000000u;
+    const auto xr = __builtin_amdgcn_make_buffer_rsrc(a.x.data, 0, a.x_bytes, 0x00020000);
+    const auto wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.w), 0, a.w_bytes, 0x00020000);
+    uint32_t xrel[CONV1D_XN];
+#pragma unroll
+    for (int u = 0; u < CONV1D_XN; ++u) {
+        const int e = tid + 256 * u;
+        const int ic = e / xw, q = e - ic * xw;
+        const int64_t pos = base + q;
+        const bool ok = e < EX && pos >= 0 && pos < a.L;
+        xrel[u] = ok ? (uint32_t)(pos * a.x.nb[0] + (int64_t)ic * a.x.nb[1]) : OOB;
+    }
+    // thread t < R stages kernel element r = t (R <= 256, host-checked)
+    const int wicl = tid < R ? tid / K : -1;
+    const uint32_t wrel = tid < R ? (uint32_t)(((int64_t)oc * a.woc + (int64_t)(tid - wicl * K) * a.wk + (int64_t)wicl * a.wic) * esz) : OOB;
+    float xv[CONV1D_XN], wv;
+    auto fetch = [&](int ic0) {
+        const int nic = min(icc, (int)(a.IC - ic0));
+        const uint32_t xc = (uint32_t)((int64_t)ic0 * a.x.nb[1]);
+        const uint32_t wc = (uint32_t)((int64_t)ic0 * a.wic * esz);
+#pragma unroll
+        for (int u = 0; u < CONV1D_XN; ++u) {
+            const uint32_t off = (xrel[u] == OOB || tid + 256 * u >= nic * xw) ? OOB : xrel[u] + xc;
+            xv[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, off, 0, 0));
+        }
+        const uint32_t off = (wrel == OOB || wicl >= nic) ? OOB : wrel + wc;
+        if (W16) wv = __half2float(__builtin_bit_cast(__half, __builtin_amdgcn_raw_buffer_load_b16(wr, off, 0, 0)));
+        else wv = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wr, off, 0, 0));
+    };
+    double acc[NP];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) acc[j] = 0.0;
+    fetch(0);
+    for (int ic0 = 0; ic0 < a.IC; ic0 += icc) {
+        const int nic = min(icc, (int)(a.IC - ic0));
+        // f16 rounding (im2col's dst type / MUL_MAT's vec_dot_type) on the way into LDS
+#pragma unroll
+        for (int u = 0; u < CONV1D_XN; ++u)
+            if (tid + 256 * u < EX) xs[tid + 256 * u] = (double)__half2float(__float2half_rn(xv[u]));
+        if (wicl >= 0) ws[tid] = (double)(W16 ? wv : __half2float(__float2half_rn(wv)));
+        __syncthreads();
+        if (ic0 + icc < a.IC) fetch(ic0 + icc);
+        const double * xp = xs + tid;
+        for (int icl = 0; icl < nic; ++icl, xp += xw)
+            for (int k = 0; k < K; ++k) {
+                const double w = ws[icl * K + k];
+#pragma unroll
+                for (int j = 0; j < NP; ++j) acc[j] = __builtin_fma(xp[k * d + 256 * j], w, acc[j]);
+            }
+        __syncthreads();
+    }
+    const float bias = BIAS ? a.bias[(int64_t)oc * a.bcs] : 0.f;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const int64_t ol = ol0 + tid + 256 * j;
+        if (ol >= a.OL) continue;
+        const float res = RES ? a.res[ol + (int64_t)oc * a.rcs] : 0.f;
+        a.y[ol + (int64_t)oc * a.ycs] = conv1d_epilogue<BIAS, RES>(acc[j], bias, res);
+    }
+}
+
+// Geometry of k_conv1d_f64v for a conv, or false where it does not apply: s = 1, a window of at most
+// 256 * CONV1D_XN doubles per input channel, a chunk's kernel slice of at most 256 taps.
+static bool conv1d_vfma_geometry(const Conv1dArgs & a, int * xw, int * icc, size_t * lds) {
+    if (a.s != 1 || a.K < 1 || a.K > 64 || a.OC > 65535) return false;
+    const int64_t w = 256 * CONV1DV_NP + (int64_t)(a.K - 1) * a.d;
+    if (w > 256 * CONV1D_XN) return false;
+    int c = (int)std::min<int64_t>(std::min<int64_t>(a.IC, 256 * CONV1D_XN / w), 256 / a.K);
+    if (c < 1) return false;
+    *xw = (int)w, *icc = c, *lds = ((size_t)c * (size_t)w + (size_t)c * a.K) * sizeof(double);
+    return true;
 }
 
 bool conv1d_fused_ok(int64_t IC, int K, int s, int d, size_t * lds) {
@@ -529,26 +636,40 @@ void launch_conv1d_fused(tts_hip_backend * be, Conv1dArgs a) {
         a.res = nullptr;
     }
     const int sel = (a.w16 ? 4 : 0) | (a.bias ? 2 : 0) | (a.res ? 1 : 0);
-    if (be->conv_acc_mode == 2) switch (sel) {
-        case 0: hipLaunchKernelGGL((k_conv1d_f64<false, false, false, true>), grid, dim3(256), lds, be->stream, a); break;
-        case 1: hipLaunchKernelGGL((k_conv1d_f64<false, false, true, true>), grid, dim3(256), lds, be->stream, a); break;
-        case 2: hipLaunchKernelGGL((k_conv1d_f64<false, true, false, true>), grid, dim3(256), lds, be->stream, a); break;
-        case 3: hipLaunchKernelGGL((k_conv1d_f64<false, true, true, true>), grid, dim3(256), lds, be->stream, a); break;
-        case 4: hipLaunchKernelGGL((k_conv1d_f64<true, false, false, true>), grid, dim3(256), lds, be->stream, a); break;
-        case 5: hipLaunchKernelGGL((k_conv1d_f64<true, false, true, true>), grid, dim3(256), lds, be->stream, a); break;
-        case 6: hipLaunchKernelGGL((k_conv1d_f64<true, true, false, true>), grid, dim3(256), lds, be->stream, a); break;
-        default: hipLaunchKernelGGL((k_conv1d_f64<true, true, true, true>), grid, dim3(256), lds, be->stream, a); break;
+#define TTS_CONV1D_SEL(KERNEL, GRID, LDS, ...)                                                                           \
+    switch (sel) {                                                                                                        \
+        case 0: hipLaunchKernelGGL((KERNEL<false, false, false __VA_ARGS__>), GRID, dim3(256), LDS, be->stream, a); break; \
+        case 1: hipLaunchKernelGGL((KERNEL<false, false, true __VA_ARGS__>), GRID, dim3(256), LDS, be->stream, a); break;  \
+        case 2: hipLaunchKernelGGL((KERNEL<false, true, false __VA_ARGS__>), GRID, dim3(256), LDS, be->stream, a); break;  \
+        case 3: hipLaunchKernelGGL((KERNEL<false, true, true __VA_ARGS__>), GRID, dim3(256), LDS, be->stream, a); break;   \
+        case 4: hipLaunchKernelGGL((KERNEL<true, false, false __VA_ARGS__>), GRID, dim3(256), LDS, be->stream, a); break;  \
+        case 5: hipLaunchKernelGGL((KERNEL<true, false, true __VA_ARGS__>), GRID, dim3(256), LDS, be->stream, a); break;   \
+        case 6: hipLaunchKernelGGL((KERNEL<true, true, false __VA_ARGS__>), GRID, dim3(256), LDS, be->stream, a); break;   \
+        default: hipLaunchKernelGGL((KERNEL<true, true, true __VA_ARGS__>), GRID, dim3(256), LDS, be->stream, a); break;   \
     }
-    else switch (sel) {
-        case 0: hipLaunchKernelGGL((k_conv1d_f64<false, false, false>), grid, dim3(256), lds, be->stream, a); break;
-        case 1: hipLaunchKernelGGL((k_conv1d_f64<false, false, true>), grid, dim3(256), lds, be->stream, a); break;
-        case 2: hipLaunchKernelGGL((k_conv1d_f64<false, true, false>), grid, dim3(256), lds, be->stream, a); break;
-        case 3: hipLaunchKernelGGL((k_conv1d_f64<false, true, true>), grid, dim3(256), lds, be->stream, a); break;
-        case 4: hipLaunchKernelGGL((k_conv1d_f64<true, false, false>), grid, dim3(256), lds, be->stream, a); break;
-        case 5: hipLaunchKernelGGL((k_conv1d_f64<true, false, true>), grid, dim3(256), lds, be->stream, a); break;
-        case 6: hipLaunchKernelGGL((k_conv1d_f64<true, true, false>), grid, dim3(256), lds, be->stream, a); break;
-        default: hipLaunchKernelGGL((k_conv1d_f64<true, true, true>), grid, dim3(256), lds, be->stream, a); break;
+#define TTS_COMMA ,
+    // Unsplit launches only (the short-sequence split keeps the 64-row MFMA kernel):
+    //  - TTS_HIP_OPT_CONV_VFMA: the vector-FMA kernel, one output channel per workgroup row, for s = 1
+    //    convs of fewer than 8 output channels (1, default) or of any channel count (2);
+    //  - TTS_HIP_OPT_CONV_TILE96: the 96-row MFMA tile when OC is a multiple of 96.
+    // Both rules read the shape alone, so a captured graph stays valid.
+    int vxw = 0, vicc = 0;
+    size_t vlds = 0;
+    if (nz == 1 && be->conv_acc_mode != 2 && be->conv_vfma && (be->conv_vfma == 2 || a.OC < 8) && conv1d_vfma_geometry(a, &vxw, &vicc, &vlds)) {
+        a.xw = vxw, a.icc = vicc;
+        const dim3 vgrid((unsigned)((a.OL + 256 * CONV1DV_NP - 1) / (256 * CONV1DV_NP)), (unsigned)a.OC);
+        TTS_CONV1D_SEL(k_conv1d_f64v, vgrid, vlds)
+    } else if (nz == 1 && be->conv_acc_mode != 2 && be->conv_tile96 && a.OC % 96 == 0) {
+        grid.y = (unsigned)(a.OC / 96);
+        lds += 32 * (size_t)a.rs * 4;  // 96 kernel rows instead of 64 (at most 41 KB in all)
+        TTS_CONV1D_SEL(k_conv1d_f64, grid, lds, TTS_COMMA false TTS_COMMA 3)
+    } else if (be->conv_acc_mode == 2) {
+        TTS_CONV1D_SEL(k_conv1d_f64, grid, lds, TTS_COMMA true)
+    } else {
+        TTS_CONV1D_SEL(k_conv1d_f64, grid, lds)
     }
+#undef TTS_COMMA
+#undef TTS_CONV1D_SEL
     TTS_HIP_CHECK(hipGetLastError());
     if (a.part) launch_split_reduce(be, (int)grid.z, a.OL, a.OC, e.y, e.ycs, e.bias, e.bcs, e.res, e.rcs);
     if (a.copy_dst)  // the output aliased the input: the kernel wrote a staging buffer

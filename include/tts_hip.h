@@ -385,6 +385,12 @@ enum tts_hip_option {
     TTS_HIP_OPT_CONV_TILE96 = 54, /* 1 (default) = unsplit fused conv_1d launches whose OC is a multiple of 96 (every DAC-44k decoder
                                      width) run 96-row workgroup tiles (four waves of 48 x 32) instead of 64-row ones; each output's
                                      MFMAs are the same in the same order: bit-identical.  0 = 64-row tiles */
+    TTS_HIP_OPT_CONV_PACK = 55,   /* 1 (default) = unsplit f64-MFMA fused conv_1d launches whose kernel is a constant leaf stage it from
+                                     a packed image (f16-rounded, zero-padded, in the LDS order of k_conv1d_f64p), made once per
+                                     (weight, tile geometry) and packed again whenever the weight's bytes are written through this
+                                     API; costs the conv weights' size again as f32.  Same chunks, same MFMA order: bit-identical.
+                                     0 = every workgroup rounds and scatters its slice itself (k_conv1d_f64).  The environment
+                                     variable TTS_HIP_OPT_CONV_PACK sets the default */
     TTS_HIP_OPT_COALESCE = 37,    /* 1 (default): while the process-wide coalescer is on (tts_hip_coalesce_enable), this
                                      backend's graph_compute of a one-prompt decode step may join the same step of other
                                      backends on the device as one coalesced launch (tts_hip_coalesce_stats); 0 = never */
@@ -480,7 +486,8 @@ int tts_hip_sample_step(tts_hip_backend_t backend, const float * logits, int32_t
 /* Whether tts_hip_sample_step covers (cfg, V): runners sample on the host otherwise. */
 int tts_sampling_device_ok(const tts_sampling * cfg, int32_t V);
 /* Diagnostic counters since creation: out[0] HIP-graph exec updates, [1] instantiations,
- * [2] fused LSTM chains, [3] fused LSTM steps.  Returns the number written (<= n). */
+ * [2] fused LSTM chains, [3] fused LSTM steps, [4]-[7] host nanoseconds (plan wait, planning, recording, exec update),
+ * [8] packed conv kernel images alive in the process, [9] their bytes.  Returns the number written (<= n). */
 int tts_hip_counters(tts_hip_backend_t backend, int64_t * out, int n);
 
 /* Raw kernel entry points for micro-benchmarks (device pointers, current backend stream).

@@ -51,6 +51,18 @@ struct BufRec {
 std::map<const char *, BufRec> g_buffers;                // base -> record (ordered: range lookups)
 std::unordered_map<const void *, uint8_t *> g_tiled;     // weight -> its tile-layout copy
 std::atomic<size_t> g_tiled_n{0};
+// Packed conv kernel images (conv_pack_get): key -> image.  An image lives as long as its source's buffer and
+// its backend; its address never changes (recorded graphs hold it), a write to the source packs it again.
+struct PackRec {
+    float * img = nullptr;
+    size_t src_bytes = 0;  // the source's span from key.w
+};
+std::map<tts::ConvPackKey, PackRec> g_packs;
+std::atomic<size_t> g_packs_n{0};
+std::atomic<size_t> g_packs_bytes{0};
+// hull of the packed sources (grown under g_reg_mu, reset when the table empties): a write outside it -- every
+// decode step's inputs -- is dismissed without taking the lock
+std::atomic<uintptr_t> g_packs_lo{UINTPTR_MAX}, g_packs_hi{0};
 }  // namespace
 
 namespace tts {
@@ -65,6 +77,71 @@ static std::atomic<int> g_coalesce_on{[] {
     return e && e[0] == '0' ? 0 : 1;
 }()};
 bool coalesce_enabled() { return g_coalesce_on.load(std::memory_order_relaxed) != 0; }
+const float * conv_pack_get(tts_hip_backend * be, const ConvPackKey & k) {
+    std::lock_guard<std::mutex> lk(g_reg_mu);
+    auto it = g_packs.find(k);
+    if (it != g_packs.end()) return it->second.img;
+    if (be->capturing) return nullptr;
+    PackRec r;
+    const size_t es = k.w16 ? 2 : 4;
+    r.src_bytes = (size_t)((k.K - 1) * k.wk + (k.IC - 1) * k.wic + (k.OC - 1) * k.woc + 1) * es;
+    const size_t bytes = k.floats() * sizeof(float);
+    if (hipMalloc((void **)&r.img, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    launch_conv1d_pack(be->stream, k, r.img);
+    g_packs[k] = r;
+    g_packs_lo.store(std::min(g_packs_lo.load(), (uintptr_t)k.w));
+    g_packs_hi.store(std::max(g_packs_hi.load(), (uintptr_t)k.w + r.src_bytes));
+    g_packs_n.store(g_packs.size(), std::memory_order_release);
+    g_packs_bytes.fetch_add(bytes, std::memory_order_relaxed);
+    return r.img;
+}
+void conv_pack_written(tts_hip_backend * be, const void * p, size_t n) {
+    if (g_packs_n.load(std::memory_order_acquire) == 0) return;
+    const char * a = (const char *)p;
+    if ((uintptr_t)a >= g_packs_hi.load() || (uintptr_t)a + n <= g_packs_lo.load()) return;
+    std::lock_guard<std::mutex> lk(g_reg_mu);
+    for (auto & e : g_packs) {
+        const char * w = (const char *)e.first.w;
+        if (!(w < a + n && a < w + e.second.src_bytes)) continue;
+        const tts_hip_backend * ob = e.first.be;
+        if (ob->device == be->device) {
+            launch_conv1d_pack(be->stream, e.first, e.second.img);
+        } else {  // written through a backend of another device: after the write, on the owner's device and stream
+            hipStreamSynchronize(be->stream);
+            hipSetDevice(ob->device);
+            launch_conv1d_pack(ob->stream, e.first, e.second.img);
+            hipSetDevice(be->device);
+        }
+    }
+}
+// be != null: every image of that backend (it is being freed); else the images whose source lies in [p, p + n).
+// The device is synchronised first: a graph on any stream may still read an image.
+void conv_pack_freed(const tts_hip_backend * be, const void * p, size_t n) {
+    if (g_packs_n.load(std::memory_order_acquire) == 0) return;
+    const char * a = (const char *)p;
+    std::vector<float *> dead;
+    {
+        std::lock_guard<std::mutex> lk(g_reg_mu);
+        for (auto it = g_packs.begin(); it != g_packs.end();) {
+            const char * w = (const char *)it->first.w;
+            if (be ? it->first.be == be : (w >= a && w < a + n)) {
+                dead.push_back(it->second.img);
+                g_packs_bytes.fetch_sub(it->first.floats() * sizeof(float), std::memory_order_relaxed);
+                it = g_packs.erase(it);
+            } else {
+                ++it;
+            }
+        }
+        if (g_packs.empty()) g_packs_lo.store(UINTPTR_MAX), g_packs_hi.store(0);
+        g_packs_n.store(g_packs.size(), std::memory_order_release);
+    }
+    if (dead.empty()) return;
+    hipDeviceSynchronize();
+    for (float * c : dead) hipFree(c);
+}
 bool buffer_lookup(const void * p, const char ** base, size_t * size) {
     std::lock_guard<std::mutex> lk(g_reg_mu);
     auto it = g_buffers.upper_bound((const char *)p);
@@ -118,6 +195,8 @@ tts_hip_backend_t tts_hip_backend_init(int device) {
     TTS_HIP_CHECK(hipMalloc((void **)&be->conv_stage, be->conv_stage_floats * sizeof(float)));
     if (const char * e = getenv("TTS_HIP_OPT_CONV_VFMA"))  // the option's default
         if (e[0] >= '0' && e[0] <= '2' && !e[1]) be->conv_vfma = e[0] - '0';
+    if (const char * e = getenv("TTS_HIP_OPT_CONV_PACK"))
+        if (e[0] >= '0' && e[0] <= '1' && !e[1]) be->conv_pack = e[0] - '0';
     be->conv_part_doubles = (size_t)8 << 20;  // 64 MiB of f64 partial sums
     TTS_HIP_CHECK(hipMalloc((void **)&be->conv_part, be->conv_part_doubles * sizeof(double)));
     be->lstm_floats = kLstmFloats;
@@ -140,6 +219,7 @@ void tts_hip_backend_free(tts_hip_backend_t be) {
     tts::coalesce_backend_gone(be);
     hipSetDevice(be->device);
     hipStreamSynchronize(be->stream);
+    tts::conv_pack_freed(be, nullptr, 0);
     for (auto & p : be->ev_pending) {
         hipEventDestroy(p.first);
         hipEventDestroy(p.second);
@@ -285,6 +365,7 @@ void tts_hip_buffer_free(tts_hip_backend_t be, void * ptr) {
     }
     if (known) {
         drop_tiled_copies(ptr, r.size);
+        tts::conv_pack_freed(nullptr, ptr, r.size);
         tts::coalesce_written(ptr, r.size);  // the coalescer's equal-content records over the range go
     }
     hipFree(ptr);
@@ -305,6 +386,8 @@ int tts_hip_tensor_set(tts_hip_backend_t be, void * dst, const void * src, size_
         if (st != 0) return st;
     } else if (hipMemcpyAsync(dst, src, size, hipMemcpyHostToDevice, be->stream) != hipSuccess) {
         return TTS_STATUS_FAILED;
+    } else {
+        tts::conv_pack_written(be, dst, size);  // (the staged copy above: tensor_set_async has done it)
     }
     if (hipStreamSynchronize(be->stream) != hipSuccess) return TTS_STATUS_FAILED;
     return 0;
@@ -342,6 +425,7 @@ int tts_hip_tensor_set_async(tts_hip_backend_t be, void * dst, const void * src,
     }
     memcpy(be->pin + off, src, size);
     if (hipMemcpyAsync(dst, be->pin + off, size, hipMemcpyHostToDevice, be->stream) != hipSuccess) return TTS_STATUS_FAILED;
+    tts::conv_pack_written(be, dst, size);  // packed conv kernels over the range: packed again, after the copy
     hipEvent_t ev;
     if (be->pin_events.empty()) {
         if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return TTS_STATUS_FAILED;
@@ -401,6 +485,7 @@ int tts_hip_copy_stream(tts_hip_backend_t be, void * dst, const void * src, size
     hipSetDevice(be->device);
     be->rb_clear();
     tts::launch_copy_stream(be, dst, src, (int64_t)(size / 16));
+    tts::conv_pack_written(be, dst, size);
     return hipGetLastError() == hipSuccess ? 0 : TTS_STATUS_FAILED;
 }
 
@@ -410,6 +495,7 @@ int tts_hip_tensor_copy(tts_hip_backend_t be, void * dst, const void * src, size
     be->rb_clear();
     tts::coalesce_written(dst, size);
     tts::launch_copy_bytes(be, dst, src, size);  // a kernel, not a blit: ~2 us less host time per step
+    tts::conv_pack_written(be, dst, size);
     return hipGetLastError() == hipSuccess ? 0 : TTS_STATUS_FAILED;
 }
 
@@ -418,7 +504,9 @@ int tts_hip_memset(tts_hip_backend_t be, void * dst, int value, size_t size) {
     hipSetDevice(be->device);
     be->rb_clear();
     tts::coalesce_written(dst, size);
-    return hipMemsetAsync(dst, value, size, be->stream) == hipSuccess ? 0 : TTS_STATUS_FAILED;
+    if (hipMemsetAsync(dst, value, size, be->stream) != hipSuccess) return TTS_STATUS_FAILED;
+    tts::conv_pack_written(be, dst, size);
+    return 0;
 }
 
 int tts_hip_synchronize(tts_hip_backend_t be) {
@@ -771,6 +859,7 @@ extern "C" int tts_hip_set_option(tts_hip_backend_t be, int option, int value) {
         case TTS_HIP_OPT_CONV_SPLIT: be->conv_split = value < 0 ? 1 : value; return 0;
         case TTS_HIP_OPT_CONV_VFMA: be->conv_vfma = value < 0 || value > 2 ? 1 : value; return 0;
         case TTS_HIP_OPT_CONV_TILE96: be->conv_tile96 = value != 0; return 0;
+        case TTS_HIP_OPT_CONV_PACK: be->conv_pack = value != 0; return 0;
         case TTS_HIP_OPT_PROFILE_GEMV: be->profile_gemv = value != 0; return 0;
         case TTS_HIP_OPT_GRAPHS: be->use_graphs = value != 0; return 0;
         case TTS_HIP_OPT_CONV_F32ACC:
@@ -884,10 +973,11 @@ extern "C" int tts_hip_set_option(tts_hip_backend_t be, int option, int value) {
 
 extern "C" int tts_hip_counters(tts_hip_backend_t be, int64_t * out, int n) {
     if (!be || !out) return TTS_STATUS_BAD_ARG;
-    const int64_t v[8] = {be->graph_updates, be->graph_instantiations, be->lstm_chains, be->lstm_steps, be->plan_wait_ns,
-                          be->cap_plan_ns, be->cap_launch_ns, be->cap_update_ns};
+    // [8], [9]: the process's packed conv kernel images (conv_pack_get) alive now, and their bytes
+    const int64_t v[10] = {be->graph_updates, be->graph_instantiations, be->lstm_chains, be->lstm_steps, be->plan_wait_ns,
+                           be->cap_plan_ns, be->cap_launch_ns, be->cap_update_ns, (int64_t)g_packs_n.load(), (int64_t)g_packs_bytes.load()};
     int k = 0;
-    for (; k < n && k < 8; ++k) out[k] = v[k];
+    for (; k < n && k < 10; ++k) out[k] = v[k];
     return k;
 }
 

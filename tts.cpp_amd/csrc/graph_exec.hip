@@ -1515,6 +1515,8 @@ struct Planner {
     // general_neural_audio_codec.cpp:133-149; build_kokoro_generator_res_block,
     // kokoro/model.cpp:136-165) -> one implicit-GEMM kernel that never writes the im2col matrix.
     static const tts_tensor * through_view(const tts_tensor * t) { return t && t->op == TTS_OP_RESHAPE ? t->src[0] : t; }
+    bool wr_hull = false;  // wr_lo / wr_hi computed: the hull of the memory this graph's nodes write
+    const char *wr_lo = nullptr, *wr_hi = nullptr;
     void try_conv(int i) {
         const tts_tensor * col = nodes[i];
         const tts_tensor *kern = col->src[0], *x = col->src[1];
@@ -1616,6 +1618,23 @@ struct Planner {
         const size_t wb = tbytes(kern);
         if (xb >= 0x80000000u || wb >= 0x80000000u) return plan_reject("conv", 12);  // 32-bit buffer offsets
         a.x_bytes = (uint32_t)xb, a.w_bytes = (uint32_t)wb;
+        // a packed image (conv_pack_get) stands for the kernel only while nothing but the host API writes it: a
+        // leaf in a live buffer of its own allocation that no node of this graph writes
+        // (a kernel outside the hull of everything the graph writes -- a weight buffer beside the compute arena
+        // -- needs no pass over the nodes: Kokoro's graphs have thousands)
+        a.w_stable = kern->op == TTS_OP_NONE && !(kern->flags & (TTS_FLAG_HOSTDATA | TTS_FLAG_OUTPUT)) && buffer_lookup(kern->data, nullptr, nullptr);
+        if (a.w_stable && !wr_hull) {
+            wr_hull = true;
+            for (int j = 0; j < n; ++j) {
+                if (is_view(nodes[j]->op) || !nodes[j]->data) continue;
+                const char * lo = (const char *)nodes[j]->data;
+                wr_lo = wr_lo ? std::min(wr_lo, lo) : lo;
+                wr_hi = std::max(wr_hi, lo + tbytes(nodes[j]));
+            }
+        }
+        if (a.w_stable && wr_lo && (const char *)kern->data < wr_hi && (const char *)kern->data + wb > wr_lo)
+            for (int j = 0; a.w_stable && j < n; ++j)
+                if (!is_view(nodes[j]->op) && nodes[j]->data && overlap(nodes[j], kern)) a.w_stable = 0;
         Item it;
         it.kind = Item::CONV;
         it.conv = a;
@@ -2980,20 +2999,43 @@ static bool capture_worthy(tts_hip_backend * be, tts_tensor * const * nodes, int
     return true;
 }
 
+// The packed kernel images a graph's fused convs will ask for (launch_conv1d_fused) are made on the compute
+// stream before the graph is recorded: an allocation and a launch that must not become part of the recording.
+// Graphs without an IM2COL (every decode step) cost one pass over the node list.
+namespace tts {
+static void plan_setup(Planner & pl, const tts_hip_backend * be);
+}
+static void conv_pack_prepare(tts_hip_backend * be, tts_tensor * const * nodes, int n_nodes) {
+    if (!be->conv_pack || !(be->fusion & TTS_FUSE_CONV)) return;
+    bool any = false;
+    for (int i = 0; i < n_nodes && !any; ++i) any = nodes[i]->op == TTS_OP_IM2COL;
+    if (!any) return;
+    Planner pl;
+    plan_setup(pl, be);
+    pl.build(nodes, n_nodes);
+    for (const Item & it : pl.items) {
+        ConvPackKey k;
+        if (it.kind == Item::CONV && conv1d_pack_key(be, it.conv, &k)) (void)conv_pack_get(be, k);
+    }
+}
+
 // Record the graph's launches into `ex` without running them.  Topology is stable from step to
 // step (only shapes/offsets move with the KV length), so the executable graph is updated in place
 // (hipGraphExecUpdate) and re-instantiated only when that fails.
 static int capture_into(tts_hip_backend * be, tts_tensor * const * nodes, int n_nodes, hipGraphExec_t & ex) {
     // record on a stream of its own: beginning a capture on the compute stream would first wait
     // for the step still running there, and the whole point of a prepared plan is to overlap it
+    conv_pack_prepare(be, nodes, n_nodes);
     hipStream_t run = be->stream;
     be->stream = be->cap_stream;
+    be->capturing = true;
     const auto t0 = std::chrono::steady_clock::now();
     TTS_HIP_CHECK(hipStreamBeginCapture(be->stream, hipStreamCaptureModeThreadLocal));
     const int st = graph_compute_launches(be, nodes, n_nodes);
     hipGraph_t graph = nullptr;
     TTS_HIP_CHECK(hipStreamEndCapture(be->stream, &graph));
     be->stream = run;
+    be->capturing = false;
     const auto t1 = std::chrono::steady_clock::now();
     be->cap_launch_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count();
     if (st != 0) {

@@ -537,6 +537,8 @@ struct tts_hip_backend {
     size_t conv_part_doubles = 0;
     int conv_vfma = 1;   // TTS_HIP_OPT_CONV_VFMA: 0 = never, 1 = convs of fewer than 8 output channels, 2 = wherever it applies
     int conv_tile96 = 1;  // TTS_HIP_OPT_CONV_TILE96: the 96-row tile of the fused conv_1d when OC % 96 == 0
+    int conv_pack = 1;    // TTS_HIP_OPT_CONV_PACK: unsplit fused conv_1d launches stage the kernel from its packed image
+    bool capturing = false;  // capture_into is recording: no allocation, no launch outside the recorded graph
     int conv_split = 1;  // TTS_HIP_OPT_CONV_SPLIT: 1 = split short convolutions to ~512 workgroups, N > 1 = to ~N, 0 = never
     int fusion = 0x3FFF;  // bitmask of TTS_FUSE_* patterns (all on)
     bool profile_gemv = false;
@@ -681,6 +683,8 @@ struct Conv1dArgs {
     uint32_t x_bytes = 0, w_bytes = 0;  // buffer-descriptor ranges (reads past them return 0)
     double * part = nullptr;        // split launch: f64 partial sums [gridDim.z][OC][OL], no epilogue
     int ic_per_split = 0;           // input channels per split (a multiple of icc)
+    int w_stable = 0;               // planner: the kernel is a leaf no node of the graph writes (it may have a packed image)
+    const float * wimg = nullptr;   // launcher: the kernel's packed image (conv_pack_get), read by k_conv1d_f64p
 };
 constexpr int CONV1D_XN = 16, CONV1D_WN = 16;  // staged elements per thread (x window, kernel slice)
 inline int conv1d_icc(int64_t IC, int K, int xw) {  // input channels per LDS chunk
@@ -699,6 +703,40 @@ inline int conv1d_icc(int64_t IC, int K, int xw) {  // input channels per LDS ch
     return best;  // 0: the shape does not fit (K > 64 or a window too wide)
 }
 bool conv1d_fused_ok(int64_t IC, int K, int s, int d, size_t * lds);
+// The packed image of a conv kernel [K, IC, OC] for one tile geometry (oct rows per channel tile, icc input
+// channels per chunk, the chunk's reduction padded to rp = 32 or 64): per (channel tile, chunk) the oct x rp
+// slice k_conv1d_f64 stages -- f16-rounded floats, zero past the chunk's icc * K taps, past IC and past OC
+// -- in the order k_conv1d_f64p holds it in LDS, [16-row tile][16 reduction slots][lane][4]: lane
+// (kq = lane >> 4, c16 = lane & 15) finds row 16 t + c16's slots 16 g + 4 j + kq, j = 0..3, as 16
+// contiguous bytes, the A operands of its MFMA steps 4 (g & 1) + j of batch g >> 1.  A slice is a straight
+// 16-byte-per-thread copy into LDS.  This function alone defines the layout (pack kernel and conv kernel).
+__host__ __device__ inline int64_t conv1d_pack_index(int nchunk, int oct, int rp, int ct, int chunk, int row, int r) {
+    const int lane = (r & 3) * 16 + (row & 15);
+    return (int64_t)(ct * nchunk + chunk) * oct * rp + ((((row >> 4) * (rp >> 4) + (r >> 4)) * 64 + lane) * 4 + ((r >> 2) & 3));
+}
+struct ConvPackKey {  // one image: the backend that owns it, the source bytes' layout, the tile geometry
+    const tts_hip_backend * be;
+    const void * w;
+    int w16, K, oct, icc, rp;
+    int64_t IC, OC, wk, wic, woc;
+    bool operator<(const ConvPackKey & o) const {
+        return std::tie(be, w, w16, K, oct, icc, rp, IC, OC, wk, wic, woc) <
+               std::tie(o.be, o.w, o.w16, o.K, o.oct, o.icc, o.rp, o.IC, o.OC, o.wk, o.wic, o.woc);
+    }
+    int nchunk() const { return (int)((IC + icc - 1) / icc); }
+    int ntile() const { return (int)((OC + oct - 1) / oct); }
+    size_t floats() const { return (size_t)ntile() * nchunk() * oct * rp; }
+};
+void launch_conv1d_pack(hipStream_t stream, const ConvPackKey & k, float * img);  // k_conv.hip
+// The image table (backend.hip).  get: the image of `k`, made on be->stream at the first request (null while a
+// graph is being recorded and the image does not exist yet, or when memory is short: the caller stages as before).
+// written: a write of [p, p + n) through `be` was queued on its stream -- every image whose source overlaps is
+// packed again, into the same buffer, on that stream.  freed: the sources in [p, p + n) are gone, their images too.
+const float * conv_pack_get(tts_hip_backend * be, const ConvPackKey & k);
+void conv_pack_written(tts_hip_backend * be, const void * p, size_t n);
+void conv_pack_freed(const tts_hip_backend * be, const void * p, size_t n);
+// The image launch_conv1d_fused will ask for (k_conv.hip), or false where this launch keeps k_conv1d_f64's staging.
+bool conv1d_pack_key(const tts_hip_backend * be, const Conv1dArgs & a, ConvPackKey * k);
 // AdaIN (+ snake) per channel row: y[c][t] = snake((norm(x[c])[t] * (1 + g[c])...) -- see k_fused.hip
 struct AdainArgs {
     const float * x = nullptr;   // NORM input rows: x[c * xcs + t], t < T

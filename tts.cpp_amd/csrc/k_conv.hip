@@ -314,6 +314,55 @@ __device__ __forceinline__ float conv1d_epilogue(double acc, float bias, float r
     return v;
 }
 
+// A workgroup's outputs of k_conv1d_f64 / k_conv1d_f64p: the split launch's partial sums, or the epilogue.
+template <bool BIAS, bool RES, bool H32, int MT>
+__device__ __forceinline__ void conv1d_store(const Conv1dArgs & a, const f64x4_t (&acc)[MT][2], int64_t ol0, int oc0, int wr0, int wc0, int c16,
+                                             int kq) {
+    if (a.part) {  // partial sums of this split, no epilogue (k_split_reduce adds bias and residual)
+#pragma unroll
+        for (int tj = 0; tj < 2; ++tj) {
+            const int64_t ol = ol0 + wc0 + 16 * tj + c16;
+            if (ol >= a.OL) continue;
+#pragma unroll
+            for (int ti = 0; ti < MT; ++ti)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int oc = oc0 + wr0 + 16 * ti + (H32 ? 4 * kq + e : kq + 4 * e);
+                    if (oc < a.OC) a.part[((int64_t)blockIdx.z * a.OC + oc) * a.OL + ol] = acc[ti][tj][e];
+                }
+        }
+        return;
+    }
+    // epilogue: bias and residual operands fetched for all 32 outputs first (clamped, branchless)
+    float bv[MT][4], rv[2][MT][4];
+#pragma unroll
+    for (int ti = 0; ti < MT; ++ti)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            // accumulator row of register e: f64 MFMA (lane >> 4) + 4e, f32 MFMA 4 (lane >> 4) + e
+            const int oc = min(oc0 + wr0 + 16 * ti + (H32 ? 4 * kq + e : kq + 4 * e), (int)a.OC - 1);
+            bv[ti][e] = BIAS ? a.bias[(int64_t)oc * a.bcs] : 0.f;
+#pragma unroll
+            for (int tj = 0; tj < 2; ++tj) {
+                const int64_t ol = min(ol0 + wc0 + 16 * tj + c16, a.OL - 1);
+                rv[tj][ti][e] = RES ? a.res[ol + (int64_t)oc * a.rcs] : 0.f;
+            }
+        }
+#pragma unroll
+    for (int tj = 0; tj < 2; ++tj) {
+        const int64_t ol = ol0 + wc0 + 16 * tj + c16;
+        if (ol >= a.OL) continue;
+#pragma unroll
+        for (int ti = 0; ti < MT; ++ti)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int oc = oc0 + wr0 + 16 * ti + (H32 ? 4 * kq + e : kq + 4 * e);
+                if (oc >= a.OC) continue;
+                a.y[ol + (int64_t)oc * a.ycs] = conv1d_epilogue<BIAS, RES>(acc[ti][tj][e], bv[ti][e], rv[tj][ti][e]);
+            }
+    }
+}
+
 template <bool W16, bool BIAS, bool RES, bool H32 = false, int MT = 2>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 1 : 2))) void k_conv1d_f64(Conv1dArgs a) {
     constexpr int OCT = 32 * MT, WN = CONV1D_WN * MT / 2;  // workgroup rows, staged kernel elements per thread
@@ -463,49 +512,143 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 1
         }
         __syncthreads();
     }
-    if (a.part) {  // partial sums of this split, no epilogue (k_split_reduce adds bias and residual)
+    conv1d_store<BIAS, RES, H32, MT>(a, acc, ol0, oc0, wr0, wc0, c16, kq);
+}
+
+// The packed image of a conv kernel (conv1d_pack_index, hip_internal.h), written once per weight tensor:
+// thread e owns element (slice, row, r) of the image, read from the source through its strides, rounded
+// to f16 and stored as f32 -- the value k_conv1d_f64 computes per workgroup and chunk.
+__global__ __launch_bounds__(256) void k_conv1d_pack(ConvPackKey k, float * __restrict__ img, int nchunk, int64_t n) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    const int per = k.oct * k.rp;
+    const int slice = (int)(e / per), w = (int)(e - (int64_t)slice * per);
+    const int ct = slice / nchunk, chunk = slice - ct * nchunk;
+    const int row = w / k.rp, r = w - row * k.rp;
+    const int icl = r / k.K, tap = r - icl * k.K;
+    const int64_t oc = (int64_t)ct * k.oct + row, ic = (int64_t)chunk * k.icc + icl;
+    float v = 0.f;
+    if (icl < k.icc && ic < k.IC && oc < k.OC) {
+        const int64_t o = oc * k.woc + (int64_t)tap * k.wk + ic * k.wic;
+        v = k.w16 ? __half2float(((const __half *)k.w)[o]) : __half2float(__float2half_rn(((const float *)k.w)[o]));
+    }
+    img[conv1d_pack_index(nchunk, k.oct, k.rp, ct, chunk, row, r)] = v;
+}
+
+void launch_conv1d_pack(hipStream_t stream, const ConvPackKey & k, float * img) {
+    const int64_t n = (int64_t)k.floats();
+    hipLaunchKernelGGL(k_conv1d_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, k, img, k.nchunk(), n);
+    TTS_HIP_CHECK(hipGetLastError());
+}
+
+// k_conv1d_f64 (f64 MFMA, unsplit) with the kernel slice staged from the packed image: a chunk's slice is
+// OCT * Rp / 1024 16-byte loads and LDS stores per thread, no address table, no rounding, and the MFMA loop
+// reads a lane's A operands of four steps as one 16-byte LDS read.  The x window is staged as before, but
+// only the ceil(icc * xw / 256) elements per thread the chunk has.  Chunks, the reduction index r of every
+// MFMA step and its k slot are k_conv1d_f64's, so every output's f64 sum -- and the result -- is the same.
+template <bool BIAS, bool RES, int MT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 1 : 2))) void k_conv1d_f64p(Conv1dArgs a) {
+    constexpr int OCT = 32 * MT, WQ = 2 * MT;  // workgroup rows, 16-byte kernel-slice pieces per thread at Rp = 64
+    extern __shared__ float sm[];
+    __shared__ int xoff[CONV1D_MAX_R];  // r -> x-window slot (ic*xw + k*d), zero slot past R
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c16 = lane & 15, kq = lane >> 4;
+    const int64_t ol0 = (int64_t)blockIdx.x * 64;
+    const int oc0 = blockIdx.y * OCT;
+    const int K = a.K, s = a.s, icc = a.icc, xw = a.xw;
+    const int R = icc * K, Rp = (R + 31) & ~31;
+    f32x4_t * ws4 = (f32x4_t *)sm;  // the slice in the image's order: [OCT / 16][Rp / 16][64 lanes] x 4 floats
+    float * xs = sm + OCT * Rp;   // [icc][xw] + 1 zero slot
+    const int zslot = icc * xw;
+    for (int r = tid; r < Rp; r += 256) {
+        const int ic = r / K, k = r - ic * K;
+        xoff[r] = r < R ? ic * xw + k * a.d : zslot;
+    }
+    if (tid == 0) xs[zslot] = 0.f;
+    __syncthreads();
+    const int wr0 = (wave >> 1) * 16 * MT, wc0 = (wave & 1) * 32;
+    const bool wave_live = oc0 + wr0 < a.OC && ol0 + wc0 < a.OL;  // wave-uniform
+    f64x4_t acc[MT][2] = {};
+    const int64_t base = ol0 * s - a.p;
+    const int EX = icc * xw;
+    const int nx = (EX + 255) >> 8;           // x elements per thread (workgroup-uniform)
+    const int nw = Rp == 64 ? WQ : WQ / 2;    // slice pieces per thread: OCT * Rp / 4 / 256
+    const int G = Rp >> 4;
+    const uint32_t OOB = 0x80000000u;
+    const auto xr = __builtin_amdgcn_make_buffer_rsrc(a.x.data, 0, a.x_bytes, 0x00020000);
+    uint32_t xrel[CONV1D_XN];
 #pragma unroll
-        for (int tj = 0; tj < 2; ++tj) {
-            const int64_t ol = ol0 + wc0 + 16 * tj + c16;
-            if (ol >= a.OL) continue;
+    for (int u = 0; u < CONV1D_XN; ++u) {
+        const int e = tid + 256 * u;
+        const int ic = e / xw, q = e - ic * xw;
+        const int64_t pos = base + q;
+        const bool ok = e < EX && pos >= 0 && pos < a.L;
+        xrel[u] = ok ? (uint32_t)(pos * a.x.nb[0] + (int64_t)ic * a.x.nb[1]) : OOB;
+    }
+    const int nchunk = (int)((a.IC + icc - 1) / icc);
+    const int slice4 = OCT * Rp / 4;
+    const f32x4_t * wp = (const f32x4_t *)a.wimg + (int64_t)blockIdx.y * nchunk * slice4 + tid;  // this thread's pieces of chunk 0
+    float xv[CONV1D_XN];
+    f32x4_t wv[WQ];
+    auto fetch = [&](int ic0) {
+        const int nic = min(icc, (int)(a.IC - ic0));
+        const uint32_t xc = (uint32_t)((int64_t)ic0 * a.x.nb[1]);
 #pragma unroll
-            for (int ti = 0; ti < MT; ++ti)
+        for (int u = 0; u < CONV1D_XN; ++u)
+            if (u < nx) {
+                const uint32_t off = (xrel[u] == OOB || tid + 256 * u >= nic * xw) ? OOB : xrel[u] + xc;
+                xv[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, off, 0, 0));
+            }
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int oc = oc0 + wr0 + 16 * ti + (H32 ? 4 * kq + e : kq + 4 * e);
-                    if (oc < a.OC) a.part[((int64_t)blockIdx.z * a.OC + oc) * a.OL + ol] = acc[ti][tj][e];
+        for (int u = 0; u < WQ; ++u)
+            if (u < nw) wv[u] = wp[256 * u];
+        wp += slice4;
+    };
+    fetch(0);
+    for (int ic0 = 0; ic0 < a.IC; ic0 += icc) {
+#pragma unroll
+        for (int u = 0; u < CONV1D_XN; ++u)
+            if (u < nx && tid + 256 * u < EX) xs[tid + 256 * u] = __half2float(__float2half_rn(xv[u]));
+#pragma unroll
+        for (int u = 0; u < WQ; ++u)
+            if (u < nw) ws4[tid + 256 * u] = wv[u];
+        __syncthreads();
+        if (ic0 + icc < a.IC) fetch(ic0 + icc);
+        if (!wave_live) {  // as k_conv1d_f64: the wave only stages
+            __syncthreads();
+            continue;
+        }
+        for (int r0 = 0; r0 < Rp; r0 += 32) {
+            int xo[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) xo[u] = xoff[r0 + 4 * u + kq];
+            float af[8][MT], bf[8][2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int t = 0; t < MT; ++t) {
+                    // row wr0 + 16 t + c16, slots r0 + 16 h + 4 j + kq (conv1d_pack_index): steps u = 4 h + j
+                    const f32x4_t v = ws4[(((wr0 >> 4) + t) * G + (r0 >> 4) + h) * 64 + lane];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) af[4 * h + j][t] = v[j];
                 }
-        }
-        return;
-    }
-    // epilogue: bias and residual operands fetched for all 32 outputs first (clamped, branchless)
-    float bv[MT][4], rv[2][MT][4];
 #pragma unroll
-    for (int ti = 0; ti < MT; ++ti)
+            for (int u = 0; u < 8; ++u) {
+                const bool z = xo[u] == zslot;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            // accumulator row of register e: f64 MFMA (lane >> 4) + 4e, f32 MFMA 4 (lane >> 4) + e
-            const int oc = min(oc0 + wr0 + 16 * ti + (H32 ? 4 * kq + e : kq + 4 * e), (int)a.OC - 1);
-            bv[ti][e] = BIAS ? a.bias[(int64_t)oc * a.bcs] : 0.f;
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj) {
-                const int64_t ol = min(ol0 + wc0 + 16 * tj + c16, a.OL - 1);
-                rv[tj][ti][e] = RES ? a.res[ol + (int64_t)oc * a.rcs] : 0.f;
+                for (int t = 0; t < 2; ++t) bf[u][t] = xs[z ? zslot : xo[u] + (wc0 + 16 * t + c16) * s];
             }
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+#pragma unroll
+                for (int ti = 0; ti < MT; ++ti)
+#pragma unroll
+                    for (int tj = 0; tj < 2; ++tj)
+                        acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)af[u][ti], (double)bf[u][tj], acc[ti][tj], 0, 0, 0);
         }
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj) {
-        const int64_t ol = ol0 + wc0 + 16 * tj + c16;
-        if (ol >= a.OL) continue;
-#pragma unroll
-        for (int ti = 0; ti < MT; ++ti)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int oc = oc0 + wr0 + 16 * ti + (H32 ? 4 * kq + e : kq + 4 * e);
-                if (oc >= a.OC) continue;
-                a.y[ol + (int64_t)oc * a.ycs] = conv1d_epilogue<BIAS, RES>(acc[ti][tj][e], bv[ti][e], rv[tj][ti][e]);
-            }
+        __syncthreads();
     }
+    conv1d_store<BIAS, RES, false, MT>(a, acc, ol0, oc0, wr0, wc0, c16, kq);
 }
 
 // conv_1d (s = 1) on f64 vector FMAs for convs of very few output channels (the DAC output conv, OC = 1,
@@ -614,7 +757,30 @@ bool conv1d_fused_ok(int64_t IC, int K, int s, int d, size_t * lds) {
     return bytes <= 64 * 1024;
 }
 
+// The image a launch of this conv stages its kernel from, or false where it keeps k_conv1d_f64's staging: a
+// kernel the planner could not prove constant, the H32 mode, a split launch, the vector-FMA kernel.  The rule
+// reads the shape and the options alone (launch_conv1d_fused's own rules, restated).
+bool conv1d_pack_key(const tts_hip_backend * be, const Conv1dArgs & a0, ConvPackKey * k) {
+    if (!be->conv_pack || !a0.w_stable || be->conv_acc_mode == 2) return false;
+    Conv1dArgs a = a0;
+    a.xw = 63 * a.s + (a.K - 1) * a.d + 1;
+    a.icc = conv1d_icc(a.IC, a.K, a.xw);
+    if (a.icc < 1) return false;
+    const int64_t tiles = ((a.OL + 63) / 64) * ((a.OC + 63) / 64), nchunk = (a.IC + a.icc - 1) / a.icc;
+    if (split_count(be, tiles, nchunk, 2, a.OL * a.OC) > 1) return false;
+    int vxw = 0, vicc = 0;
+    size_t vlds = 0;
+    if (be->conv_vfma && (be->conv_vfma == 2 || a.OC < 8) && conv1d_vfma_geometry(a, &vxw, &vicc, &vlds)) return false;
+    k->be = be, k->w = a.w, k->w16 = a.w16, k->K = a.K;
+    k->oct = be->conv_tile96 && a.OC % 96 == 0 ? 96 : 64;
+    k->icc = a.icc, k->rp = (a.icc * a.K + 31) & ~31;
+    k->IC = a.IC, k->OC = a.OC, k->wk = a.wk, k->wic = a.wic, k->woc = a.woc;
+    return true;
+}
+
 void launch_conv1d_fused(tts_hip_backend * be, Conv1dArgs a) {
+    ConvPackKey pk;
+    a.wimg = conv1d_pack_key(be, a, &pk) ? conv_pack_get(be, pk) : nullptr;
     a.xw = 63 * a.s + (a.K - 1) * a.d + 1;
     a.icc = conv1d_icc(a.IC, a.K, a.xw);
     a.rs = ((a.icc * a.K + 31) & ~31) + 1;
@@ -659,6 +825,20 @@ void launch_conv1d_fused(tts_hip_backend * be, Conv1dArgs a) {
         a.xw = vxw, a.icc = vicc;
         const dim3 vgrid((unsigned)((a.OL + 256 * CONV1DV_NP - 1) / (256 * CONV1DV_NP)), (unsigned)a.OC);
         TTS_CONV1D_SEL(k_conv1d_f64v, vgrid, vlds)
+    } else if (a.wimg) {  // conv1d_pack_key: unsplit, f64 MFMA, not the vector kernel's -- the tile is the image's
+        const size_t plds = ((size_t)pk.oct * pk.rp + (size_t)a.icc * a.xw + 1) * 4;
+        grid.y = (unsigned)pk.ntile();
+        const int psel = (pk.oct == 96 ? 4 : 0) | (a.bias ? 2 : 0) | (a.res ? 1 : 0);
+        switch (psel) {
+            case 0: hipLaunchKernelGGL((k_conv1d_f64p<false, false, 2>), grid, dim3(256), plds, be->stream, a); break;
+            case 1: hipLaunchKernelGGL((k_conv1d_f64p<false, true, 2>), grid, dim3(256), plds, be->stream, a); break;
+            case 2: hipLaunchKernelGGL((k_conv1d_f64p<true, false, 2>), grid, dim3(256), plds, be->stream, a); break;
+            case 3: hipLaunchKernelGGL((k_conv1d_f64p<true, true, 2>), grid, dim3(256), plds, be->stream, a); break;
+            case 4: hipLaunchKernelGGL((k_conv1d_f64p<false, false, 3>), grid, dim3(256), plds, be->stream, a); break;
+            case 5: hipLaunchKernelGGL((k_conv1d_f64p<false, true, 3>), grid, dim3(256), plds, be->stream, a); break;
+            case 6: hipLaunchKernelGGL((k_conv1d_f64p<true, false, 3>), grid, dim3(256), plds, be->stream, a); break;
+            default: hipLaunchKernelGGL((k_conv1d_f64p<true, true, 3>), grid, dim3(256), plds, be->stream, a); break;
+        }
     } else if (nz == 1 && be->conv_acc_mode != 2 && be->conv_tile96 && a.OC % 96 == 0) {
         grid.y = (unsigned)(a.OC / 96);
         lds += 32 * (size_t)a.rs * 4;  // 96 kernel rows instead of 64 (at most 41 KB in all)

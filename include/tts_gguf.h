@@ -97,13 +97,22 @@ int tts_gguf_writer_write(const tts_gguf_writer * w, const char * path); /* 0 on
 
 /* ---- quantize tool (examples/quantize/quantize_impl.cpp) ---- */
 typedef struct tts_quantize_params {
-    int32_t quantize_type;                  /* TTS_TYPE_Q4_K, TTS_TYPE_Q8_0, TTS_TYPE_Q5_0, TTS_TYPE_Q4_0 or TTS_TYPE_F16 */
+    int32_t quantize_type;                  /* TTS_TYPE_Q4_K, TTS_TYPE_Q6_K, TTS_TYPE_Q8_0, TTS_TYPE_Q5_0, TTS_TYPE_Q4_0 or TTS_TYPE_F16 */
     int32_t quantize_output_heads;          /* quantization_params fields, same meaning */
     int32_t quantize_text_embeddings;
     int32_t quantize_cross_attn_kv;
     int32_t convert_dac_to_f16;
     int32_t convert_non_quantizable_to_f16;
+    int32_t mix;                            /* 0 = every quantized tensor in quantize_type; TTS_QUANT_MIX_* */
 } tts_quantize_params;
+
+/* llama.cpp's Q4_K_M recipe: quantize_type must be TTS_TYPE_Q4_K (Parler and Orpheus files only).  Of the tensors the
+ * rule quantizes these take Q6_K instead, where more_bits(N, n) = N < n/8 || N >= 7*n/8 || (N - n/8) % 3 == 2 over the
+ * n layers of the file (integer division):
+ *   Orpheus: orpheus.layers.N.self_attn.v_proj and .mlp.down_proj when more_bits(N, n); orpheus.lm_head;
+ *   Parler : ...layers.N.self_attn.v_proj.weight, ...layers.N.fc2.weight and ...layers.N.encoder_attn.v_proj.weight
+ *            when more_bits(N, n); the *.weight.head tensors. */
+#define TTS_QUANT_MIX_Q4_K_M 1
 
 /* Rows of x [rows][K] f32 (host memory) -> type's blocks in dst (host memory); 0 on success. */
 typedef int (*tts_quantize_rows_fn)(void * ctx, int32_t type, const float * x, void * dst, int64_t rows, int64_t K);
@@ -112,6 +121,11 @@ typedef int (*tts_quantize_rows_fn)(void * ctx, int32_t type, const float * x, v
  * orpheus.layers.N.{self_attn,mlp}.*_proj and orpheus.embed_tokens, orpheus.lm_head with quantize_output_heads,
  * never a norm, orpheus.rope_frequencies or a snac.* tensor): 1 = quantize, 2 = convert to F16, 0 = copy unchanged. */
 int tts_gguf_tensor_rule(const char * arch, const char * name, const tts_quantize_params * params);
+/* The storage type the tool gives tensor `name` of an F32 file of n_layers layers: quantize_type (or TTS_TYPE_Q6_K
+ * where params->mix moves it) for rule 1, TTS_TYPE_F16 for rule 2 and for rule 1 under quantize_type F16,
+ * TTS_TYPE_F32 for a tensor copied unchanged.  Negative: an unknown architecture, or parameters the tool refuses
+ * (TTS_STATUS_BAD_ARG: a mix with another quantize_type than Q4_K, a mix for a Dia or Kokoro file, Q6_K for Kokoro). */
+int32_t tts_gguf_tensor_out_type(const char * arch, const char * name, int32_t n_layers, const tts_quantize_params * params);
 /* quantize_gguf: KV pairs copied + general.quantization_version / general.quantization_type, every
  * tensor in file order, quantized rows from `fn`, F16 by round-to-nearest-even.  0 on success. */
 int tts_gguf_quantize(const char * in_path, const char * out_path, const tts_quantize_params * params,

@@ -155,7 +155,8 @@ typedef struct tts_orpheus_config {
     float rope_low_freq_factor;   /* 1 */
     float rope_high_freq_factor;  /* 4 */
     int32_t rope_original_ctx;    /* 8192 */
-    int32_t pad_;
+    int32_t weight_mix;           /* synthetic runner only, with weight_type Q4_K: TTS_QUANT_MIX_Q4_K_M (tts_gguf.h) gives the
+                                   * tensors that recipe names (v_proj, down_proj of its layers, the head) Q6_K; 0 = uniform */
 } tts_orpheus_config;
 
 typedef struct tts_orpheus tts_orpheus;

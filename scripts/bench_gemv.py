@@ -11,6 +11,10 @@ difference has to clear).
 bench_gemv.py q4 [reps] [rounds] [M list] [cold]: the same with the slots Q8_0, Q5_0, Q4_0, Q8_0 again.  Cold:
 every type's launches rotate through enough copies that 512 MiB of the smallest type's weights pass between two
 uses of one copy.
+
+bench_gemv.py q6 [reps] [rounds] [M list] [cold] [shape names]: Q6_K beside Q4_K and Q8_0 on the Parler and Orpheus
+matrices (Q6_K_SHAPES), slots Q8_0, Q4_K, Q6_K, Q8_0 again; times are per tts_hip_gemv call (a call may be several
+launches).
 """
 import json
 import os
@@ -39,12 +43,86 @@ SHAPES = [  # (name, type, K, N)
 Q5_SHAPES = [(1024, 1024), (1024, 4096), (4096, 1024), (2048, 2048), (2048, 8192)]  # (K, N)
 
 
-def quant_bytes(rng, wt, K, N):
-    """Random blocks of type wt with a small finite fp16 d."""
+Q6_K_SHAPES = [("parler_qkvo", 1024, 1024), ("parler_fc1", 1024, 4096), ("parler_fc2", 4096, 1024), ("orpheus_q", 3072, 3072),
+               ("orpheus_up", 3072, 8192), ("orpheus_down", 8192, 3072), ("orpheus_head", 3072, 156940)]  # (name, K, N)
+
+
+def quant_bytes(rng, wt, K, N, dmin=False):
+    """Random blocks of type wt with a small finite fp16 d (Q6_K: d is the block's last field; dmin: Q4_K's dmin too,
+    which the q6 mode sets and the older modes, which never pass Q4_K, do not)."""
     bs = ttship.TYPE_SIZE[wt]
     w = rng.integers(0, 256, size=ttship.row_size(wt, K) * N, dtype=np.uint8)
-    w.reshape(-1, bs)[:, 0:2] = np.frombuffer(np.float16(1e-3).tobytes(), dtype=np.uint8)
+    d = np.frombuffer(np.float16(1e-3).tobytes(), dtype=np.uint8)
+    blk = w.reshape(-1, bs)
+    if wt == ttship.Q6_K:
+        blk[:, 208:210] = d
+    else:
+        blk[:, 0:2] = d
+        if wt == ttship.Q4_K and dmin:
+            blk[:, 2:4] = d
     return w
+
+
+def compare_q6():
+    """q6 mode: per (shape, M) and round the slots Q8_0, Q4_K, Q6_K, Q8_0 again."""
+    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+    rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+    mlist = [int(v) for v in sys.argv[4].split(",")] if len(sys.argv) > 4 else [1, 2, 8, 32]
+    cold = int(sys.argv[5]) if len(sys.argv) > 5 else 1
+    only = sys.argv[6].split(",") if len(sys.argv) > 6 else None
+    hip = ttship.HipBackend(0)
+    L = ttship.lib()
+    rng = np.random.default_rng(0)
+    types = (ttship.Q8_0, ttship.Q4_K, ttship.Q6_K)
+    for name, K, N in Q6_K_SHAPES:
+        if only and name not in only:
+            continue
+        dev = {}
+        for wt in types:
+            w = quant_bytes(rng, wt, K, N, dmin=True)
+            # cold: as many copies of the SMALLEST (Q4_K) matrix as pass 512 MiB, the same count for every type
+            ncopy = -(-(512 << 20) // (ttship.row_size(ttship.Q4_K, K) * N)) if cold else 1
+            dev[wt] = [hip.alloc(w.nbytes) for _ in range(ncopy)]
+            for d in dev[wt]:
+                hip.set(d, w)
+        at = {wt: 0 for wt in types}
+        for M in mlist:
+            x = rng.standard_normal((M, K)).astype(np.float32)
+            dx, dy = hip.alloc(x.nbytes), hip.alloc(4 * M * N)
+            hip.set(dx, x)
+
+            def slot(wt, n):
+                for _ in range(n):
+                    L.tts_hip_gemv_ex(hip.ptr, wt, dev[wt][at[wt] % len(dev[wt])], dx, dy, K, N, M, 0)
+                    at[wt] += 1
+
+            for wt in dev:
+                slot(wt, 2)
+            hip.sync()
+            hip.set_option(ttship.OPT["PROFILE_GEMV"], 1)
+            order = (("q8_0_a", ttship.Q8_0), ("q4_K", ttship.Q4_K), ("q6_K", ttship.Q6_K), ("q8_0_b", ttship.Q8_0))
+            us = {key: [] for key, _ in order}
+            for _ in range(rounds):
+                for key, wt in order:
+                    hip.gemv_stats(-1, reset=True)
+                    slot(wt, reps)
+                    ms, n, _ = hip.gemv_stats(wt, reset=True)
+                    assert n >= reps, (n, reps)
+                    us[key].append(round(1000.0 * ms / reps, 2))
+            hip.set_option(ttship.OPT["PROFILE_GEMV"], 0)
+            med = {k: float(np.median(v)) for k, v in us.items()}
+            q8 = 0.5 * (med["q8_0_a"] + med["q8_0_b"])
+            b6 = ttship.row_size(ttship.Q6_K, K) * N
+            print(json.dumps({"shape": name, "K": K, "N": N, "M": M, "cold": cold, "copies": len(dev[ttship.Q6_K]), "reps": reps, "us_per_round": us,
+                              "median_us": med, "q8_0_vs_q8_0_spread_us": round(max(abs(a - b) for a, b in zip(us["q8_0_a"], us["q8_0_b"])), 2),
+                              "q6_K_over_q8_0": round(med["q6_K"] / q8, 3), "q6_K_over_q4_K": round(med["q6_K"] / med["q4_K"], 3),
+                              "q6_K_weight_GBps": round(b6 / (med["q6_K"] * 1e-6) / 1e9, 1)}), flush=True)
+            hip.free(dx)
+            hip.free(dy)
+        for ds in dev.values():
+            for d in ds:
+                hip.free(d)
+    hip.close()
 
 
 def compare_q5():
@@ -170,6 +248,8 @@ def main():
         return compare_q5()
     if len(sys.argv) > 1 and sys.argv[1] == "q4":
         return compare_q4()
+    if len(sys.argv) > 1 and sys.argv[1] == "q6":
+        return compare_q6()
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 50
     mlist = [int(v) for v in sys.argv[2].split(",")] if len(sys.argv) > 2 else [1, 8]
     tiled = int(sys.argv[3]) if len(sys.argv) > 3 else 0  # 1: Q4_K in the tile layout (matrix-core kernel)

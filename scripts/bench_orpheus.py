@@ -4,7 +4,8 @@ Synthetic weights in the exact Orpheus shapes (all matrices Q4_K, incl. embeddin
 head), prompt prefill, then timed greedy AR steps with device sampling.  Prints one JSON line:
 tokens/s, audio-s/s (82.03 Orpheus tokens per audio-second) and the dequant-GEMV
 roofline from in-packet HIP events over profiled steps.
-usage: bench_orpheus.py [batch] [steps] [prompt_len] [layers]"""
+usage: bench_orpheus.py [batch] [steps] [prompt_len] [layers] [mix]
+mix = 1: the synthetic model in the quantize tool's Q4_K_M-style mix (Q6_K v_proj / down_proj of its layers and head)."""
 import json
 import os
 import pathlib
@@ -24,7 +25,10 @@ def main():
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 64
     n_prompt = int(sys.argv[3]) if len(sys.argv) > 3 else 32
-    kw = {"n_layers": int(sys.argv[4])} if len(sys.argv) > 4 else {}
+    kw = {"n_layers": int(sys.argv[4])} if len(sys.argv) > 4 and int(sys.argv[4]) > 0 else {}
+    mix = int(sys.argv[5]) if len(sys.argv) > 5 else 0
+    if mix:
+        kw["weight_mix"] = ttship.QUANT_MIX_Q4_K_M
     be = ttship.HipBackend(0)
     if os.environ.get("TTS_BENCH_GRAPHS") is not None:  # 0: eager launches (rocprofv3 kernel traces)
         be.set_option(ttship.OPT["GRAPHS"], int(os.environ["TTS_BENCH_GRAPHS"]))
@@ -53,7 +57,7 @@ def main():
     avg_us = 1000.0 * ms / max(launches, 1)
     gbs = nbytes / max(launches, 1) / (avg_us * 1e-6) / 1e9
     print(json.dumps({
-        "workload": f"Orpheus-3B Q4_K greedy decode, {B} prompts, {cfg.n_layers} layers, prompt {n_prompt}",
+        "workload": f"Orpheus-3B {'Q4_K_M-style mix' if mix else 'Q4_K'} greedy decode, {B} prompts, {cfg.n_layers} layers, prompt {n_prompt}",
         "tokens_per_s": round(B * steps / dt, 1), "audio_sec_per_s": round(B * steps / dt / TOK_PER_AUDIO_S, 3),
         "ms_per_step": round(1000 * dt / steps, 3), "graph_nodes": o.last_graph_nodes(),
         "weight_GB": round(o.weight_bytes() / 1e9, 3), "load_s": round(t_load, 1),

@@ -832,7 +832,8 @@ int tts_hip_supports_op(const tts_tensor * n) {
         case TTS_OP_GET_ROWS:
             return n->src[1]->type == TTS_TYPE_I32 &&
                    (n->src[0]->type == TTS_TYPE_F32 || n->src[0]->type == TTS_TYPE_F16 || n->src[0]->type == TTS_TYPE_Q4_K ||
-                    n->src[0]->type == TTS_TYPE_Q8_0 || n->src[0]->type == TTS_TYPE_Q5_0 || n->src[0]->type == TTS_TYPE_Q4_0);
+                    n->src[0]->type == TTS_TYPE_Q8_0 || n->src[0]->type == TTS_TYPE_Q5_0 || n->src[0]->type == TTS_TYPE_Q4_0 ||
+                    (n->src[0]->type == TTS_TYPE_Q6_K && n->src[0]->ne[0] % 256 == 0));
         case TTS_OP_MUL_MAT: {
             const tts_tensor * a = n->src[0];
             const tts_tensor * b = n->src[1];
@@ -840,7 +841,7 @@ int tts_hip_supports_op(const tts_tensor * n) {
             // ggml_can_mul_mat: src1 broadcasts over src0 in dims 2 and 3
             if (a->ne[0] != b->ne[0] || b->ne[2] % a->ne[2] || b->ne[3] % a->ne[3]) return 0;
             if (a->type == TTS_TYPE_F32 || a->type == TTS_TYPE_F16) return 1;
-            if (a->type == TTS_TYPE_Q4_K) return a->ne[0] % 256 == 0;
+            if (a->type == TTS_TYPE_Q4_K || a->type == TTS_TYPE_Q6_K) return a->ne[0] % 256 == 0;
             if (a->type == TTS_TYPE_Q8_0 || a->type == TTS_TYPE_Q5_0 || a->type == TTS_TYPE_Q4_0) return a->ne[0] % 32 == 0;
             return 0;
         }

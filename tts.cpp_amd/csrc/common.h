@@ -1,7 +1,7 @@
 // Internal definitions shared by the HIP backend, the graph builder and the runners.
 // Block formats follow ggml's (Q4_K: ggml-common.h block_q4_K, 144 B / 256 weights;
 // Q8_0: block_q8_0, 34 B / 32 weights; Q5_0: block_q5_0, 22 B / 32 weights;
-// Q4_0: block_q4_0, 18 B / 32 weights) so that weight bytes produced by TTS.cpp's loader
+// Q4_0: block_q4_0, 18 B / 32 weights; Q6_K: block_q6_K, 210 B / 256 weights) so that weight bytes produced by TTS.cpp's loader
 // (/root/reference/src/models/loaders.cpp:79-88) are consumed unchanged.
 #pragma once
 
@@ -54,6 +54,20 @@ struct block_q4_0 {
     uint8_t qs[QK4_0 / 2];
 };
 static_assert(sizeof(block_q4_0) == 18, "q4_0 block");
+
+// weight e = 128 h + 32 g + l (h = 0, 1; g = 0 .. 3; l = 0 .. 31) = d * scales[e / 16] * (v - 32) with the 6-bit
+// v = nibble (g >> 1) of ql[64 h + 32 (g & 1) + l] | (bits 2 g, 2 g + 1 of qh[32 h + l]) << 4.  210 = 2 mod 4: rows of
+// an odd number of blocks leave every other row 2-byte aligned only
+struct block_q6_K {
+    uint8_t ql[QK_K / 2];
+    uint8_t qh[QK_K / 4];
+    int8_t scales[QK_K / 16];
+    uint16_t d;
+};
+static_assert(sizeof(block_q6_K) == 210, "q6_K block");
+
+// the K-quants, whose products quantize src1 to Q8_K
+TTS_HD bool wtype_q8k_act(int t) { return t == TTS_TYPE_Q4_K || t == TTS_TYPE_Q6_K; }
 
 // the activation type a weight type's products quantize src1 to (ggml's vec_dot_type): Q4_0, Q5_0 and Q8_0
 // all take Q8_0

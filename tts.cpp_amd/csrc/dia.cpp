@@ -104,12 +104,12 @@ static std::string dia_file_name(const std::string & name) {
 
 // kind: 0 = matrix, 1 = norm weight (~1), 3 = embedding.  With a file attached the tensor takes the file's
 // storage type where the quantize tool's Dia rule (quantize_impl.cpp:42-49) can have put it: F32, F16, Q8_0,
-// Q5_0 or Q4_0 for a matrix, an embedding or a head, F32 for a norm.
+// Q5_0, Q4_0 or Q6_K for a matrix, an embedding or a head, F32 for a norm.
 static tts_tensor * wnew(tts_dia * p, int type, int64_t ne0, int64_t ne1, int kind, const std::string & name) {
     if (p->w.gguf) {
         type = p->w.file_type(name, TTS_TYPE_F32);
         const bool ok = type == TTS_TYPE_F32 || (kind != 1 && (type == TTS_TYPE_F16 || type == TTS_TYPE_Q8_0 || type == TTS_TYPE_Q5_0 ||
-                                                               type == TTS_TYPE_Q4_0));
+                                                               type == TTS_TYPE_Q4_0 || type == TTS_TYPE_Q6_K));
         if (!ok && p->type_err.empty())
             p->type_err = "gguf: tensor '" + p->w.gguf_name(name) + "' has type " + std::to_string(type) + ", which a Dia file cannot hold there";
         if (!ok) type = TTS_TYPE_F32;

@@ -13,6 +13,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -604,6 +605,58 @@ int tts_gguf_tensor_rule(const char * arch_c, const char * name_c, const tts_qua
     return 0;
 }
 
+// llama.cpp's use_more_bits
+static bool more_bits(int i, int n) { return i < n / 8 || i >= 7 * n / 8 || (i - n / 8) % 3 == 2; }
+
+// the N of "...layers.N." (-1 when the name has none)
+static int layer_of(const std::string & n) {
+    const size_t a = n.find("layers.");
+    if (a == std::string::npos) return -1;
+    size_t b = a + 7;
+    if (b >= n.size() || n[b] < '0' || n[b] > '9') return -1;
+    long v = 0;
+    for (; b < n.size() && n[b] >= '0' && n[b] <= '9' && v < 1000000; ++b) v = v * 10 + (n[b] - '0');
+    return b < n.size() && n[b] == '.' ? (int)v : -1;
+}
+
+// what the parameters ask of an architecture's files: 0, or the status the tool refuses them with
+static int params_status(const std::string & arch, const tts_quantize_params * p) {
+    if (p->mix != 0) {
+        if (p->mix != TTS_QUANT_MIX_Q4_K_M || p->quantize_type != TTS_TYPE_Q4_K) return TTS_STATUS_BAD_ARG;
+        if (arch != "parler-tts" && arch != "orpheus") return TTS_STATUS_BAD_ARG;
+    }
+    if (arch == "kokoro" && p->quantize_type == TTS_TYPE_Q6_K) return TTS_STATUS_BAD_ARG;  // its widths are no multiples of 256
+    return TTS_STATUS_SUCCESS;
+}
+
+// a tensor the rule quantizes, under TTS_QUANT_MIX_Q4_K_M
+static bool mix_q6(const std::string & arch, const std::string & n, int n_layers) {
+    const int l = layer_of(n);
+    const bool mb = l >= 0 && more_bits(l, n_layers);
+    if (arch == "orpheus") {
+        if (n == "orpheus.lm_head" || n == "orpheus.lm_head.weight") return true;
+        if (!starts_with(n, "orpheus.layers.")) return false;
+        return mb && (ends_with(n, ".self_attn.v_proj") || ends_with(n, ".mlp.down_proj") || ends_with(n, ".self_attn.v_proj.weight") ||
+                      ends_with(n, ".mlp.down_proj.weight"));
+    }
+    if (!starts_with(n, "decoder.")) return false;  // Parler's own tensors, never the codec's
+    if (ends_with(n, "weight.head")) return true;
+    return mb && (ends_with(n, ".self_attn.v_proj.weight") || ends_with(n, ".fc2.weight") || ends_with(n, ".encoder_attn.v_proj.weight"));
+}
+
+int32_t tts_gguf_tensor_out_type(const char * arch_c, const char * name_c, int32_t n_layers, const tts_quantize_params * p) {
+    if (!p || !name_c) return TTS_STATUS_BAD_ARG;
+    const std::string arch = arch_c ? arch_c : "parler-tts";
+    const int rule = tts_gguf_tensor_rule(arch_c, name_c, p);
+    if (rule < 0) return rule;
+    const int st = params_status(arch, p);
+    if (st != TTS_STATUS_SUCCESS) return st;
+    if (rule == 0) return TTS_TYPE_F32;
+    if (rule == 2 || p->quantize_type == TTS_TYPE_F16) return TTS_TYPE_F16;
+    if (p->mix == TTS_QUANT_MIX_Q4_K_M && mix_q6(arch, name_c, n_layers)) return TTS_TYPE_Q6_K;
+    return p->quantize_type;
+}
+
 // ggml_fp32_to_fp16: round to nearest even, subnormals, overflow to inf, NaN kept quiet
 static uint16_t f32_to_f16(float f) {
     uint32_t x;
@@ -628,9 +681,9 @@ static uint16_t f32_to_f16(float f) {
 }
 
 int tts_gguf_quantize(const char * in_path, const char * out_path, const tts_quantize_params * p, tts_quantize_rows_fn fn, void * fn_ctx) {
-    if (!p || (p->quantize_type != TTS_TYPE_Q4_K && p->quantize_type != TTS_TYPE_Q8_0 && p->quantize_type != TTS_TYPE_Q5_0 &&
-               p->quantize_type != TTS_TYPE_Q4_0 && p->quantize_type != TTS_TYPE_F16)) {
-        fprintf(stderr, "gguf quantize: type must be Q4_K, Q8_0, Q5_0, Q4_0 or F16\n");
+    if (!p || (p->quantize_type != TTS_TYPE_Q4_K && p->quantize_type != TTS_TYPE_Q6_K && p->quantize_type != TTS_TYPE_Q8_0 &&
+               p->quantize_type != TTS_TYPE_Q5_0 && p->quantize_type != TTS_TYPE_Q4_0 && p->quantize_type != TTS_TYPE_F16)) {
+        fprintf(stderr, "gguf quantize: type must be Q4_K, Q6_K, Q8_0, Q5_0, Q4_0 or F16\n");
         return TTS_STATUS_BAD_ARG;
     }
     tts_gguf * g = tts_gguf_open(in_path);
@@ -638,6 +691,25 @@ int tts_gguf_quantize(const char * in_path, const char * out_path, const tts_qua
     std::string arch = "parler-tts";  // only parler-tts files lack general.architecture (:188)
     const int64_t ak = tts_gguf_find_key(g, "general.architecture");
     if (ak >= 0 && tts_gguf_get_str(g, ak)) arch = tts_gguf_get_str(g, ak);
+    if (params_status(arch, p) != TTS_STATUS_SUCCESS) {
+        fprintf(stderr, "gguf quantize: type %d with mix %d is not available for a '%s' file\n", p->quantize_type, p->mix, arch.c_str());
+        tts_gguf_close(g);
+        return TTS_STATUS_BAD_ARG;
+    }
+    // the mix's layer count: the file's key, else the largest N of a "...layers.N." tensor + 1
+    int32_t n_layers = 0;
+    if (p->mix != 0) {
+        const char * keys[] = {"orpheus.layers", "parler-tts.decoder.num_hidden_layers", "num_hidden_layers"};
+        for (const char * k : keys) {
+            const int64_t ki = tts_gguf_find_key(g, k);
+            uint32_t v;
+            if (n_layers == 0 && ki >= 0 && tts_gguf_get_u32(g, ki, &v)) n_layers = (int32_t)v;
+        }
+        const char * pre = arch == "orpheus" ? "orpheus.layers." : "decoder.layers.";  // the decoder's layers only
+        if (n_layers == 0)
+            for (int64_t i = 0; i < tts_gguf_n_tensors(g); ++i)
+                if (starts_with(tts_gguf_tensor_name(g, i), pre)) n_layers = std::max(n_layers, layer_of(tts_gguf_tensor_name(g, i)) + 1);
+    }
     int st = TTS_STATUS_SUCCESS;
     tts_gguf_writer * w = tts_gguf_writer_new();
     tts_gguf_copy_kv(w, g);
@@ -673,7 +745,7 @@ int tts_gguf_quantize(const char * in_path, const char * out_path, const tts_qua
             break;
         }
         if (rule == 1 && p->quantize_type != TTS_TYPE_F16) {
-            new_type = p->quantize_type;
+            new_type = p->mix != 0 && mix_q6(arch, name, n_layers) ? TTS_TYPE_Q6_K : p->quantize_type;
             const int64_t bs = tts_gguf_blck_size(new_type);
             if (ne[0] % bs) {
                 fprintf(stderr, "gguf quantize: tensor '%s' row length %lld is not a multiple of %lld\n", name.c_str(), (long long)ne[0],

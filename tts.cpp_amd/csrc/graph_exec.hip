@@ -112,7 +112,8 @@ bool is_gemv(const tts_tensor * n) {
         ((uintptr_t)b->data % 16) == 0 && (a->nb[1] % 16) == 0)
         return false;
     switch (a->type) {
-        case TTS_TYPE_Q4_K: return a->ne[0] % 256 == 0;
+        case TTS_TYPE_Q4_K:
+        case TTS_TYPE_Q6_K: return a->ne[0] % 256 == 0;
         case TTS_TYPE_Q8_0:
         case TTS_TYPE_Q5_0:
         case TTS_TYPE_Q4_0: return a->ne[0] % 32 == 0;
@@ -517,7 +518,7 @@ struct Planner {
             if (G.kind != Item::GEMV || G.ln || G.mms[0]->src[1] != L.dst) continue;
             const int wt = G.mms[0]->src[0]->type;
             const tts_tensor * B = G.mms[0]->src[1];
-            if (wt != TTS_TYPE_Q4_K && !(wtype_q80_act(wt) && q80pro && B->ne[1] * B->ne[2] * B->ne[3] <= 8)) continue;
+            if (!wtype_q8k_act(wt) && !(wtype_q80_act(wt) && q80pro && B->ne[1] * B->ne[2] * B->ne[3] <= 8)) continue;
             const int64_t K = L.dst->ne[0];
             if (K % 256 || K > 4096) continue;
             if (((uintptr_t)L.w->data & 15) || (L.b && ((uintptr_t)L.b->data & 15)) || (L.dst->nb[1] & 15)) continue;
@@ -861,6 +862,10 @@ struct Planner {
                 // not hoistable: it stays where it is, as a node passed over
             }
             if (!(mask & TTS_FUSE_GROUP)) break;
+            // a product of the same activation in another weight type (a Q6_K v_proj between Q4_K k_proj and q_proj)
+            // ends the group: a later member hoisted over it and its KV store lands on memory they still use, i.e. in
+            // backend scratch, which a coalesced step cannot take.  Each type's products run as their own items.
+            if (j > i && act[j] == 0 && mm->op == TTS_OP_MUL_MAT && mm->src[1] == x && is_gemv(mm) && mm->src[0]->type != a0->type) break;
             if (std::find(skips.begin(), skips.end(), j) != skips.end()) {  // a member's KV store: absorbed
                 ++j;
                 continue;
@@ -1656,7 +1661,7 @@ struct Planner {
         auto leaf_ok = [&](const tts_tensor * g) {
             if (g->op != TTS_OP_GET_ROWS || sole_consumer(g) != a || g->type != TTS_TYPE_F32) return false;
             const tts_tensor *tab = g->src[0], *idx = g->src[1];
-            if (tab->type != TTS_TYPE_F32 && tab->type != TTS_TYPE_F16 && tab->type != TTS_TYPE_Q8_0 && tab->type != TTS_TYPE_Q5_0 && tab->type != TTS_TYPE_Q4_0 && tab->type != TTS_TYPE_Q4_K) return false;
+            if (tab->type != TTS_TYPE_F32 && tab->type != TTS_TYPE_F16 && tab->type != TTS_TYPE_Q8_0 && tab->type != TTS_TYPE_Q5_0 && tab->type != TTS_TYPE_Q4_0 && tab->type != TTS_TYPE_Q4_K && tab->type != TTS_TYPE_Q6_K) return false;
             if (idx->type != TTS_TYPE_I32 || idx->ne[1] * idx->ne[2] * idx->ne[3] != 1 || (idx->nb[0] % 4)) return false;
             if (tab->ne[0] != root->ne[0] || g->ne[0] != root->ne[0] || tab->ne[2] * tab->ne[3] != 1) return false;
             const int64_t rows = g->ne[1] * g->ne[2] * g->ne[3], M = root->ne[1] * root->ne[2] * root->ne[3];
@@ -2313,7 +2318,7 @@ static int run_gemv_item(tts_hip_backend * be, const Item & it, const Item * xat
     }
     // Q8_0 / Q5_0 with <= 8 columns (K % 256 == 0): the same prologue, writing Q8_0 blocks (k_gemv_q8_0 / q5_0<MC, PRO>)
     const bool q80pro = wtype_q80_act(j.wtype) && j.K % QK_K == 0 && j.M <= 8 && (it.ln || be->gemv_q80_pro);
-    if (j.wtype == TTS_TYPE_Q4_K || q80pro) {
+    if (wtype_q8k_act(j.wtype) || q80pro) {
         // the kernel quantizes (and normalizes) src1 itself in every workgroup
         j.pro = it.ln ? PRO_LN : PRO_QUANT;
         j.tiled = (a0->flags & TTS_FLAG_TILED) ? 1 : 0;
@@ -2492,6 +2497,7 @@ static int run_gemv_item(tts_hip_backend * be, const Item & it, const Item * xat
             if (tmp) break;
         }
         if (jj.hetero) jj.N = 0;  // every row count comes from roff
+        if (jj.wtype == TTS_TYPE_Q6_K && !gemv_q6k_ok(jj)) return TTS_STATUS_UNSUPPORTED;
         launch_gemv_job(be, jj);
     }
     if (xattn) return run_attn_item(be, *xattn, xtab);  // unfused fallback: the attention right after its query
@@ -3369,9 +3375,10 @@ extern "C" int tts_hip_gemv_res(tts_hip_backend_t be, int type, const void * w, 
                                 int64_t K, int64_t N, int64_t M, int32_t wflags) {
     if (!be) return TTS_STATUS_BAD_ARG;
     if ((wflags & TTS_FLAG_TILED) && (type != TTS_TYPE_Q4_K || N % 4)) return TTS_STATUS_BAD_ARG;
-    if (type == TTS_TYPE_Q4_K && K % 256) return TTS_STATUS_BAD_ARG;
+    if (tts::wtype_q8k_act(type) && K % 256) return TTS_STATUS_BAD_ARG;
+    if (type == TTS_TYPE_Q6_K && ((uintptr_t)w & 1)) return TTS_STATUS_BAD_ARG;  // its blocks hold an f16 at an even offset
     if (tts::wtype_q80_act(type) && K % 32) return TTS_STATUS_BAD_ARG;
-    if (type != TTS_TYPE_Q4_K && type != TTS_TYPE_Q8_0 && type != TTS_TYPE_Q5_0 && type != TTS_TYPE_Q4_0 && type != TTS_TYPE_F16 && type != TTS_TYPE_F32) return TTS_STATUS_UNSUPPORTED;
+    if (type != TTS_TYPE_Q4_K && type != TTS_TYPE_Q6_K && type != TTS_TYPE_Q8_0 && type != TTS_TYPE_Q5_0 && type != TTS_TYPE_Q4_0 && type != TTS_TYPE_F16 && type != TTS_TYPE_F32) return TTS_STATUS_UNSUPPORTED;
     if ((type == TTS_TYPE_F32 || type == TTS_TYPE_F16) && K % 4) return TTS_STATUS_BAD_ARG;
     hipSetDevice(be->device);
     GemvJob j;
@@ -3392,7 +3399,7 @@ extern "C" int tts_hip_gemv_res(tts_hip_backend_t be, int type, const void * w, 
         j.rcs = N;
     }
     const bool q80pro = tts::wtype_q80_act(type) && K % QK_K == 0 && M <= 8 && be->gemv_q80_pro;
-    if (type == TTS_TYPE_Q4_K || q80pro) {
+    if (tts::wtype_q8k_act(type) || q80pro) {
         j.pro = PRO_QUANT;
         j.tiled = (wflags & TTS_FLAG_TILED) ? 1 : 0;
         if ((uintptr_t)x & 15) {  // the prologue reads 16-B vectors
@@ -3408,6 +3415,7 @@ extern "C" int tts_hip_gemv_res(tts_hip_backend_t be, int type, const void * w, 
         j.aq.vtype = TTS_TYPE_F32;
     }
     be->aq.src = nullptr;  // scratch overwritten
+    if (type == TTS_TYPE_Q6_K && !tts::gemv_q6k_ok(j)) return TTS_STATUS_UNSUPPORTED;
     launch_gemv_job(be, j);
     return 0;
 }

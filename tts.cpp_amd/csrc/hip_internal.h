@@ -620,6 +620,7 @@ void profile_push(tts_hip_backend * be, hipEvent_t e0, hipEvent_t e1, double byt
 // Quantize M columns (column stride xcs floats) of x to the vec_dot type of `wtype`.
 void launch_quantize_act(tts_hip_backend * be, int wtype, const float * x, int64_t xcs, int64_t K, int64_t M, ActQuant & aq);
 void launch_gemv_job(tts_hip_backend * be, const GemvJob & job);
+bool gemv_q6k_ok(const GemvJob & j);  // a Q6_K job k_gemv_q6_K can take (f32 activation for its prologue, one row count, even addresses)
 // F32 weights x many columns (k_gemm.hip): bit-identical to the sequential-f64 float dot
 bool launch_bgemm_f32(tts_hip_backend * be, const tts_tensor * node);
 bool gemm_f32_ok(const GemvJob & j);

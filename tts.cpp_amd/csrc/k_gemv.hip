@@ -1,10 +1,10 @@
-// Quantized decode GEMV for gfx950: y = W x with W in Q4_K / Q8_0 / Q5_0 / Q4_0 / F16 / F32, M <= 8 columns.
+// Quantized decode GEMV for gfx950: y = W x with W in Q4_K / Q6_K / Q8_0 / Q5_0 / Q4_0 / F16 / F32, M <= 8 columns.
 //
 // Replaces GGML_OP_MUL_MAT at every decode site (Parler model.cpp:544-546,571,583,594,601,603;
 // Dia model.cpp:535-537,...; Orpheus model.cpp:254-256,...).
 //
 // Numerics are ggml-cpu's generic scalar paths, bit for bit: the activation column is quantized to
-// the weight type's vec_dot_type (Q8_K for Q4_K, Q8_0 for Q8_0, Q5_0 and Q4_0, F16 for F16) with the exact
+// the weight type's vec_dot_type (Q8_K for Q4_K and Q6_K, Q8_0 for Q8_0, Q5_0 and Q4_0, F16 for F16) with the exact
 // quantize_row_*_ref arithmetic, the per-block integer dot products are exact (v_dot4_i32_i8), and
 // the f32 combination follows vec_dot_*'s order exactly.  F32/F16 dots take f32 products and
 // accumulate them in f64, as ggml_vec_dot_f32/f16 do (tests/test_gemv_gpu.py: bit-exact).
@@ -4162,6 +4162,226 @@ static void launch_q40s(tts_hip_backend * be, const GemvJob & j) {
     if (be->profile_gemv) profile_push(be, e0, e1, gemv_bytes(j), TTS_TYPE_Q4_0);
 }
 
+// ------------------------------------------------------------------------------------------
+// Q6_K x Q8_K GEMV / many-column product on the file's own layout (block_q6_K, 210 B per 256 weights),
+// reproducing ggml_vec_dot_q6_K_q8_K's generic order: per (row, column), blocks in ascending order,
+// aux32[l] = sum over e = l (mod 8) of scales[e / 16] * q8[e] * a[e] (integers: exact, order-free),
+// sums[l] += (d * d_x) * (float)aux32[l] with each product and the add rounded, then sumf = sums[0] + ... + sums[7].
+//
+// Lane mapping (wave64): lane = (row slot s = lane >> 3, residue l = lane & 7), so a wave owns 8 rows and a lane
+// the aux32[l] / sums[l] chains of its row for every column of the tile (MC registers).  The weights are decoded
+// once per (row, block) whatever the number of columns; a tile is up to 16 columns wide and the launch's column
+// tiles are blockIdx.z, so a many-column product is one launch whose weight decode is shared by 16 columns.
+//
+// 210 = 2 (mod 4): a row of an odd number of blocks leaves every other row 2-byte aligned only.  A wave stages the
+// current block of its 8 rows through LDS: lanes load the aligned dwords that cover each block (from the 4-byte
+// aligned address at or before it, never past the matrix' last byte) and store them as two halves shifted by the
+// block's misalignment (0 or 2), so that the staged block is 4-byte aligned in LDS whatever its address was.
+// The next block's dwords are requested before the current one is computed.
+//
+// The activation's Q8_K blocks (lane-major layout, q8k_row_block) come from the Q4_K kernels' prologue
+// (PRO_QUANT / PRO_LN), run by every workgroup for its column tile.
+// LDS: q4k_lds(MC, K) | 4 waves x 8 rows x Q6K_STAGE.
+constexpr int Q6K_BLK = 210;
+constexpr int Q6K_DW = 54;      // dwords covering a block from the aligned address at or before it (2 + 210 <= 216)
+constexpr int Q6K_STAGE = 228;  // LDS bytes per staged block (57 dwords: the 8 rows start on different banks)
+// four 6-bit values v in 0 .. 63 -> the int8 v - 32: t = v ^ 32 is v - 32 for v >= 32 and v + 32 (bit 5 set) below,
+// where v - 32 is t with 0xC0 on top; (t & 0x20) * 6 = 0xC0 stays inside its byte
+__device__ __forceinline__ uint32_t q6k_s8(uint32_t v) {
+    const uint32_t t = v ^ 0x20202020u;
+    return t | ((t & 0x20202020u) * 6u);
+}
+static size_t q6k_lds(int MC, int64_t K) {
+    const int64_t nb = K / QK_K;
+    auto a = [](size_t n) { return (n + 15) & ~(size_t)15; };
+    const size_t nslot = (size_t)MC * nb + 1;
+    return a(nslot * QK_K) + a(4 * nslot) + 16 * nslot + 4 * 8 * Q6K_STAGE;
+}
+template <int MC, int PRO>
+__global__ __launch_bounds__(256) void k_gemv_q6_K(GemvJob j) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int nb = (int)(j.K / QK_K);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int s = lane >> 3, l = lane & 7;
+    const int col0 = (int)blockIdx.z * MC;
+    const int mcols = min(MC, (int)j.M - col0);
+    const int nslot = MC * nb + 1;  // + the prologue's trash slot
+    int8_t * xq_s = (int8_t *)smem;
+    float * xd_s = (float *)(smem + al16((size_t)nslot * QK_K));
+    int16_t * xs_s = (int16_t *)((char *)xd_s + al16(sizeof(float) * nslot));
+    char * stage = (char *)xs_s + 16 * (size_t)nslot + wave * (8 * Q6K_STAGE);
+    {
+        ProOv ov;
+        ov.col0 = col0;
+        ov.mcols = mcols;
+        q4k_prologue<PRO, 16>(j, nb, xq_s, xd_s, xs_s, nullptr, nullptr, NoMid{}, ov);
+    }
+    __syncthreads();
+
+    const int mat = blockIdx.y;
+    const uint8_t * __restrict__ W = j.W[mat];
+    const uint8_t * const wend = W + (j.N - 1) * j.w_row_bytes + (int64_t)nb * Q6K_BLK;  // one past the matrix' last byte
+    const int64_t G = (j.N + 7) / 8;
+    // staging slot u of this lane: dword c of row slot r (7 x 64 slots >= 8 x 54)
+    constexpr int NU = (8 * Q6K_DW + 63) / 64;
+    for (int64_t g = (int64_t)blockIdx.x * 4 + wave; g < G; g += (int64_t)gridDim.x * 4) {
+        uint32_t pre[NU];
+        // Every dword is requested unconditionally, all of them before the first use (a load under a guard is sunk next
+        // to its use and pays its own round trip): a dword that would reach outside the matrix -- before its first
+        // byte when the matrix starts 2-byte aligned, or past its last -- reads an aligned dword inside it instead and
+        // is mended with a 2-byte load afterwards, which only the waves holding the matrix' two ends ever do.
+        const uint8_t * const wsafe = W + ((4 - ((uintptr_t)W & 3)) & 3);
+        auto fetch = [&](int b) {
+            bool edge[NU];
+#pragma unroll
+            for (int u = 0; u < NU; ++u) {
+                const int i = lane + 64 * u;
+                const int r = min(i / Q6K_DW, 7), c = i - (i / Q6K_DW) * Q6K_DW;
+                int64_t row = g * 8 + r;
+                row = row < j.N ? row : j.N - 1;
+                const uint8_t * p = W + row * j.w_row_bytes + (int64_t)b * Q6K_BLK;
+                const uint8_t * q = p - ((uintptr_t)p & 3) + 4 * c;
+                edge[u] = q < W || q + 4 > wend;
+                pre[u] = *gptr((const uint32_t *)(edge[u] ? wsafe : q));
+            }
+            TTS_PIN_LOADS();
+#pragma unroll
+            for (int u = 0; u < NU; ++u) {
+                if (__builtin_expect(edge[u], 0)) {
+                    const int i = lane + 64 * u;
+                    const int r = min(i / Q6K_DW, 7), c = i - (i / Q6K_DW) * Q6K_DW;
+                    int64_t row = g * 8 + r;
+                    row = row < j.N ? row : j.N - 1;
+                    const uint8_t * p = W + row * j.w_row_bytes + (int64_t)b * Q6K_BLK;
+                    const uint8_t * q = p - ((uintptr_t)p & 3) + 4 * c;
+                    uint32_t v = 0;
+                    if (q < W) v = (uint32_t)*(const uint16_t *)(q + 2) << 16;
+                    else if (q + 2 <= wend) v = *(const uint16_t *)q;
+                    pre[u] = v;
+                }
+            }
+        };
+        auto put = [&](int b) {
+#pragma unroll
+            for (int u = 0; u < NU; ++u) {
+                const int i = lane + 64 * u;
+                const int r = i / Q6K_DW, c = i - r * Q6K_DW;
+                int64_t row = g * 8 + r;
+                row = row < j.N ? row : j.N - 1;
+                const int off = (int)((uintptr_t)(W + row * j.w_row_bytes + (int64_t)b * Q6K_BLK) & 3);  // 0 or 2
+                const int at = 4 * c - off;  // block byte of this dword's low half
+                if (r < 8) {
+                    char * d = stage + r * Q6K_STAGE + at;
+                    if (at >= 0) *(uint16_t *)d = (uint16_t)pre[u];
+                    *(uint16_t *)(d + 2) = (uint16_t)(pre[u] >> 16);
+                }
+            }
+        };
+        float sums[MC];
+#pragma unroll
+        for (int m = 0; m < MC; ++m) sums[m] = 0.f;
+        fetch(0);
+        for (int b = 0; b < nb; ++b) {
+            put(b);
+            // LDS operations of one wave complete in order: waiting for them (not for the global loads in flight) and
+            // keeping the compiler from moving LDS accesses across is all the wave's own staging needs
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+            if (b + 1 < nb) fetch(b + 1);
+            const uint8_t * blk = (const uint8_t *)(stage + s * Q6K_STAGE);
+            // the lane's 32 weights e = 128 h + 32 gq + 8 k + l as int8, byte k of wv[4 h + gq]
+            uint32_t wv[8];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                uint32_t qa = 0, qb = 0, gh = 0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    qa |= (uint32_t)blk[64 * h + 8 * k + l] << (8 * k);
+                    qb |= (uint32_t)blk[64 * h + 32 + 8 * k + l] << (8 * k);
+                    gh |= (uint32_t)blk[128 + 32 * h + 8 * k + l] << (8 * k);
+                }
+                wv[4 * h + 0] = q6k_s8((qa & 0x0F0F0F0Fu) | ((gh & 0x03030303u) << 4));
+                wv[4 * h + 1] = q6k_s8((qb & 0x0F0F0F0Fu) | (((gh >> 2) & 0x03030303u) << 4));
+                wv[4 * h + 2] = q6k_s8(((qa >> 4) & 0x0F0F0F0Fu) | (((gh >> 4) & 0x03030303u) << 4));
+                wv[4 * h + 3] = q6k_s8(((qb >> 4) & 0x0F0F0F0Fu) | (((gh >> 6) & 0x03030303u) << 4));
+            }
+            // bytes k = 0, 1 of a dword take scales[2 q], bytes 2, 3 scales[2 q + 1] (q = the 32-element group)
+            int sc[16];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const uint32_t w4 = *(const uint32_t *)(blk + 192 + 4 * i);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) sc[4 * i + k] = (int)(int8_t)(w4 >> (8 * k));
+            }
+            const float dw = dev_fp16_to_fp32(*(const uint16_t *)(blk + 208));
+#pragma unroll
+            for (int m = 0; m < MC; ++m) {
+                if (m < mcols) {
+                    const int xb = m * nb + b;
+                    const int4 xl = *(const int4 *)(xq_s + xb * QK_K + l * 32);
+                    const int4 xh = *(const int4 *)(xq_s + xb * QK_K + l * 32 + 16);
+                    // group q = 2 c + hi lies at dword hi * 4 + c of the lane's 32 bytes
+                    const int xw[8] = {xl.x, xh.x, xl.y, xh.y, xl.z, xh.z, xl.w, xh.w};
+                    int aux = 0;
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        aux += __mul24(sc[2 * q], __builtin_amdgcn_sdot4((int)(wv[q] & 0x0000FFFFu), xw[q], 0, false));
+                        aux += __mul24(sc[2 * q + 1], __builtin_amdgcn_sdot4((int)(wv[q] & 0xFFFF0000u), xw[q], 0, false));
+                    }
+                    const float dd = __fmul_rn(dw, xd_s[xb]);
+                    sums[m] = __fadd_rn(sums[m], __fmul_rn(dd, (float)aux));
+                }
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();  // every lane has read the staged block before the next one lands on it
+        }
+        const int64_t row = g * 8 + s;
+#pragma unroll
+        for (int m = 0; m < MC; ++m) {
+            const float tot = q4k_octet_total(0.f, sums[m]);
+            if (l == 0 && m < mcols && row < j.N) gemv_store<8>(j, mat, row, col0 + m, tot);
+        }
+    }
+}
+
+template <int MC>
+static void launch_q6k_mc(tts_hip_backend * be, const GemvJob & j, unsigned tiles) {
+    const size_t lds = q6k_lds(MC, j.K);
+    const int64_t G = (j.N + 7) / 8;
+    int64_t gx = (G + 3) / 4;
+    // every workgroup pays the prologue of its column tile: at most ~2 workgroups per CU and (matrix, tile)
+    const int64_t cap = (2 * be->cus + (int64_t)j.nmat * tiles - 1) / ((int64_t)j.nmat * tiles);
+    if (gx > cap) gx = cap < 1 ? 1 : cap;
+    const dim3 grid((unsigned)gx, (unsigned)j.nmat, tiles);
+    static std::atomic<uint32_t> attr_ln{0}, attr_q{0};
+    if (j.pro == PRO_LN) {
+        if (lds > 64 * 1024) set_lds_attr_once(attr_ln, be->device, (const void *)k_gemv_q6_K<MC, PRO_LN>);
+        hipLaunchKernelGGL((k_gemv_q6_K<MC, PRO_LN>), grid, dim3(256), lds, be->stream, j);
+    } else {
+        if (lds > 64 * 1024) set_lds_attr_once(attr_q, be->device, (const void *)k_gemv_q6_K<MC, PRO_QUANT>);
+        hipLaunchKernelGGL((k_gemv_q6_K<MC, PRO_QUANT>), grid, dim3(256), lds, be->stream, j);
+    }
+}
+// One launch whatever M is: column tiles of the widest MC whose Q8_K activation fits LDS
+bool gemv_q6k_ok(const GemvJob & j) {
+    bool ok = j.x && (j.pro == PRO_QUANT || j.pro == PRO_LN) && !j.hetero && j.K % QK_K == 0 && j.w_row_bytes % 2 == 0;
+    for (int i = 0; i < j.nmat; ++i) ok = ok && ((uintptr_t)j.W[i] & 1) == 0;  // blocks at even addresses: misalignment 0 or 2
+    return ok;
+}
+static void launch_gemv_q6k(tts_hip_backend * be, const GemvJob & j) {
+    if (!gemv_q6k_ok(j)) return;  // callers check first and return a status (run_gemv_item, tts_hip_gemv_res)
+    int mc = j.M > 8 ? 16 : j.M > 4 ? 8 : j.M > 2 ? 4 : j.M > 1 ? 2 : 1;
+    while (mc > 1 && q6k_lds(mc, j.K) > 150 * 1024) mc /= 2;
+    const unsigned tiles = (unsigned)((j.M + mc - 1) / mc);
+    switch (mc) {
+        case 1: launch_q6k_mc<1>(be, j, tiles); break;
+        case 2: launch_q6k_mc<2>(be, j, tiles); break;
+        case 4: launch_q6k_mc<4>(be, j, tiles); break;
+        case 8: launch_q6k_mc<8>(be, j, tiles); break;
+        default: launch_q6k_mc<16>(be, j, tiles); break;
+    }
+}
+
 template <int MC>
 static void launch_gemv_mc(tts_hip_backend * be, const GemvJob & j) {
     const unsigned nmat = (unsigned)j.nmat;
@@ -4270,6 +4490,15 @@ void launch_gemv_job(tts_hip_backend * be, const GemvJob & job) {
     }
     if (job.wtype == TTS_TYPE_Q4_0 && job.M > 8 && job.aq.vtype == TTS_TYPE_Q8_0 && !job.hetero && be->gemm_q4_0) {
         launch_gemm_q4_0(be, job);  // one matrix-core pass instead of a GEMV launch per 8 columns
+        TTS_HIP_CHECK(hipGetLastError());
+        if (prof) {
+            TTS_HIP_CHECK(hipEventRecord(e1, be->stream));
+            profile_push(be, e0, e1, gemv_bytes(job), job.wtype);
+        }
+        return;
+    }
+    if (job.wtype == TTS_TYPE_Q6_K) {  // every column count in one launch (column tiles of up to 16)
+        launch_gemv_q6k(be, job);
         TTS_HIP_CHECK(hipGetLastError());
         if (prof) {
             TTS_HIP_CHECK(hipEventRecord(e1, be->stream));

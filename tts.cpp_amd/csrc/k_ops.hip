@@ -288,7 +288,7 @@ __global__ __launch_bounds__(256) void k_soft_max(TD dst, TD a, TD m, int mask_f
     for (int64_t i = threadIdx.x; i < nc; i += blockDim.x) dp[i] = __fmul_rn(dp[i], inv);
 }
 
-// ---- GET_ROWS (f32 / f16 / q4_K / q8_0 / q5_0 / q4_0 source, i32 index) ----
+// ---- GET_ROWS (f32 / f16 / q4_K / q6_K / q8_0 / q5_0 / q4_0 source, i32 index) ----
 // element k of a table row (dequantize_row_q4_K / q8_0 / q5_0 arithmetic for quantized tables)
 __device__ __forceinline__ float table_elem(const TD & s0, const char * src, int64_t k) {
     if (s0.type == TTS_TYPE_F32) return ((const float *)src)[k];
@@ -309,6 +309,14 @@ __device__ __forceinline__ float table_elem(const TD & s0, const char * src, int
         const int e = (int)(k % QK4_0), jq = e & 15;
         const int nib = e < 16 ? (b->qs[jq] & 0x0F) : (b->qs[jq] >> 4);
         return __fmul_rn((float)(nib - 8), __half2float(__ushort_as_half(b->d)));
+    }
+    if (s0.type == TTS_TYPE_Q6_K) {  // dequantize_row_q6_K: (d * scales[e / 16]) * (v - 32), bytes read one by one (2-byte aligned rows)
+        const uint8_t * b = (const uint8_t *)src + (k / QK_K) * (int64_t)sizeof(block_q6_K);
+        const int e = (int)(k % QK_K), h = e >> 7, gq = (e >> 5) & 3, l = e & 31;
+        const int qb = b[64 * h + 32 * (gq & 1) + l];
+        const int v = ((gq & 2 ? qb >> 4 : qb & 15) | (((b[128 + 32 * h + l] >> (2 * gq)) & 3) << 4)) - 32;
+        const float d = __half2float(__ushort_as_half((uint16_t)(b[208] | (b[209] << 8))));
+        return __fmul_rn(__fmul_rn(d, (float)(int8_t)b[192 + (e >> 4)]), (float)v);
     }
     // Q4_K: dequantize_row_q4_K
     const block_q4_K * b = (const block_q4_K *)src + k / QK_K;

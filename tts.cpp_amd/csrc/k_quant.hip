@@ -1,5 +1,5 @@
-// Weight quantizers on the device: ggml's quantize_row_q4_K_ref, quantize_row_q8_0_ref, quantize_row_q5_0_ref and
-// quantize_row_q4_0_ref
+// Weight quantizers on the device: ggml's quantize_row_q4_K_ref, quantize_row_q6_K_ref, quantize_row_q8_0_ref,
+// quantize_row_q5_0_ref and quantize_row_q4_0_ref
 // (ggml-quants.c; restated in oracle/ggml_ref.c), so f32 weights can be turned into GGUF-compatible
 // Q4_K / Q8_0 / Q5_0 / Q4_0 bytes where they live (the reference's examples/quantize path, quantize_impl.cpp:82-292,
 // does this on the CPU).  Every float operation is the reference's, in source order, rounded to f32
@@ -263,6 +263,116 @@ __global__ __launch_bounds__(256) void k_quantize_q4_0(const float * __restrict_
     }
 }
 
+// make_qx_quants(16, 32, x, L, rmse_type = 1, no weights) for one 16-value sub-block: the signed value of largest
+// magnitude (the first of equals) sets iscale = -32 / max; 18 more candidates -(32 + 0.1 is) / max, is = -9 .. 9,
+// weights x^2, the candidate maximising sumlx^2 / suml2 wins (strictly better only).  L = l + 32 in 0 .. 63.
+__device__ float q6k_search(const float (&x)[16], int (&L)[16]) {
+    float mx = 0.f, amax = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const float ax = fabsf(x[i]);
+        if (ax > amax) amax = ax, mx = x[i];
+    }
+    if (amax < 1e-15f) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) L[i] = 0;
+        return 0.f;
+    }
+    float iscale = cr_divf(-32.f, mx);
+    float sumlx = 0.f, suml2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int l = max(-32, min(31, q_nearest_int(__fmul_rn(iscale, x[i]))));
+        L[i] = l + 32;
+        const float w = __fmul_rn(x[i], x[i]);
+        sumlx = __fadd_rn(sumlx, __fmul_rn(__fmul_rn(w, x[i]), (float)l));
+        suml2 = __fadd_rn(suml2, __fmul_rn(__fmul_rn(w, (float)l), (float)l));
+    }
+    float scale = suml2 != 0.f ? cr_divf(sumlx, suml2) : 0.f;
+    float best = __fmul_rn(scale, sumlx);
+    for (int is = -9; is <= 9; ++is) {
+        if (is == 0) continue;
+        iscale = cr_divf(-__fadd_rn(32.f, __fmul_rn(0.1f, (float)is)), mx);
+        sumlx = 0.f, suml2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int l = max(-32, min(31, q_nearest_int(__fmul_rn(iscale, x[i]))));
+            const float w = __fmul_rn(x[i], x[i]);
+            sumlx = __fadd_rn(sumlx, __fmul_rn(__fmul_rn(w, x[i]), (float)l));
+            suml2 = __fadd_rn(suml2, __fmul_rn(__fmul_rn(w, (float)l), (float)l));
+        }
+        if (suml2 > 0.f && __fmul_rn(sumlx, sumlx) > __fmul_rn(best, suml2)) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) L[i] = 32 + max(-32, min(31, q_nearest_int(__fmul_rn(iscale, x[i]))));
+            scale = cr_divf(sumlx, suml2);
+            best = __fmul_rn(scale, sumlx);
+        }
+    }
+    return scale;
+}
+
+// quantize_row_q6_K_ref: 16 lanes per 256-value block, lane j owns sub-block j.  The sub-block scale of largest
+// magnitude (the first of equals) sets iscale = -128 / it and d = f16(1 / iscale); scales[j] = min(127,
+// nearest_int(iscale * scale_j)); every element is re-quantized with d * scales[j] unless that is 0 (the search's
+// L stays).  The 6-bit codes meet in LDS, from where each lane packs 8 ql bytes and 4 qh bytes.  A block whose
+// largest scale is below 1e-15 is all zeros.  Bytes are written one at a time: rows are 2-byte aligned only.
+__global__ __launch_bounds__(256) void k_quantize_q6_K(const float * __restrict__ x, uint8_t * __restrict__ dst, int64_t rows, int64_t K) {
+    __shared__ uint8_t Ls[16][256];
+    const int j = threadIdx.x & 15, lb = threadIdx.x >> 4;
+    const int64_t nbr = K / 256, nblk = rows * nbr;
+    const int64_t blk = (int64_t)blockIdx.x * 16 + lb;
+    const bool live = blk < nblk;
+    const int64_t b = live ? blk : nblk - 1;  // dead lanes shadow the last block (all lanes stay in the shuffles)
+    const float * xs = x + (b / nbr) * K + (b % nbr) * 256 + 16 * j;
+    float v[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[i] = xs[i];
+    int L[16];
+    const float scale = q6k_search(v, L);
+    // the first sub-block whose |scale| is the largest: max by magnitude, then the lowest lane holding it
+    float amax = fabsf(scale);
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
+    const unsigned long long hit = __ballot(fabsf(scale) == amax);
+    const int lane = threadIdx.x & 63;
+    const unsigned mine = (unsigned)(hit >> (lane & 48)) & 0xFFFFu;
+    const float max_scale = __shfl(scale, (lane & 48) + __ffs(mine) - 1);
+    const bool zero = amax < 1e-15f;
+    const float iscale = zero ? 0.f : cr_divf(-128.f, max_scale);
+    const uint16_t dh = zero ? (uint16_t)0 : q_fp32_to_fp16(cr_divf(1.f, iscale));
+    const int sc = zero ? 0 : min(127, q_nearest_int(__fmul_rn(iscale, scale)));
+    const float d = __fmul_rn(q_fp16_to_fp32(dh), (float)sc);
+    if (zero) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) L[i] = 0;
+    } else if (d != 0.f) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) L[i] = 32 + max(-32, min(31, q_nearest_int(cr_divf(v[i], d))));
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) Ls[lb][16 * j + i] = (uint8_t)L[i];
+    __syncthreads();
+    if (!live) return;
+    uint8_t * y = dst + b * 210;
+    const uint8_t * Lb = Ls[lb];
+    // ql[64 h + l] = L[128 h + l] & 15 | (L[128 h + l + 64] & 15) << 4, ql[64 h + 32 + l] the same from + 32 / + 96;
+    // qh[32 h + l] = the four top bit pairs.  Lane j writes ql[8 j .. 8 j + 7] and qh[4 j .. 4 j + 3].
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int q = 8 * j + i, h = q >> 6, p = (q >> 5) & 1, l = q & 31;
+        const int e = 128 * h + 32 * p + l;
+        y[q] = (uint8_t)((Lb[e] & 15) | ((Lb[e + 64] & 15) << 4));
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int q = 4 * j + i, h = q >> 5, l = q & 31;
+        const int e = 128 * h + l;
+        y[128 + q] = (uint8_t)((Lb[e] >> 4) | ((Lb[e + 32] >> 4) << 2) | ((Lb[e + 64] >> 4) << 4) | ((Lb[e + 96] >> 4) << 6));
+    }
+    y[192 + j] = (uint8_t)(int8_t)sc;
+    if (j == 0) y[208] = (uint8_t)(dh & 0xFF), y[209] = (uint8_t)(dh >> 8);
+}
+
 }  // namespace
 
 }  // namespace tts
@@ -274,6 +384,10 @@ extern "C" int tts_hip_quantize(tts_hip_backend_t be, int type, const float * x,
         if (K % 256) return TTS_STATUS_BAD_ARG;
         const int64_t threads = rows * (K / 256) * 8;
         hipLaunchKernelGGL(tts::k_quantize_q4_K, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, be->stream, x, (uint8_t *)dst, rows, K);
+    } else if (type == TTS_TYPE_Q6_K) {
+        if (K % 256) return TTS_STATUS_BAD_ARG;
+        const int64_t nblk = rows * (K / 256);
+        hipLaunchKernelGGL(tts::k_quantize_q6_K, dim3((unsigned)((nblk + 15) / 16)), dim3(256), 0, be->stream, x, (uint8_t *)dst, rows, K);
     } else if (type == TTS_TYPE_Q8_0) {
         if (K % 32) return TTS_STATUS_BAD_ARG;
         const int64_t nblk = rows * (K / 32);

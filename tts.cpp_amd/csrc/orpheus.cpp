@@ -76,7 +76,7 @@ extern "C" void tts_orpheus_default_config(tts_orpheus_config * c) {
     c->rope_low_freq_factor = 1.0f;
     c->rope_high_freq_factor = 4.0f;
     c->rope_original_ctx = 8192;
-    c->pad_ = 0;
+    c->weight_mix = 0;
 }
 
 // orpheus_gguf_encoder.prepare_rope_frequencies (py-gguf/tts_encoders/orpheus_gguf_encoder.py:144-173)
@@ -117,16 +117,25 @@ static std::string orpheus_file_name(const std::string & name) {
 }
 
 // kind: 0 = matrix, 1 = norm weight (~1), 3 = embedding, 4 = the computed rope factors.  With a file attached
-// a matrix, the embedding and the head each take the type the file gives that tensor (F32, Q4_K, Q8_0, Q5_0 or
-// Q4_0); the norms and the rope factors are F32.
+// a matrix, the embedding and the head each take the type the file gives that tensor (F32, Q4_K, Q6_K, Q8_0, Q5_0
+// or Q4_0); the norms and the rope factors are F32.
 static tts_tensor * wnew(tts_orpheus * p, int type, int64_t ne0, int64_t ne1, int kind, const std::string & name) {
     if (p->w.gguf) {
         type = p->w.file_type(name, TTS_TYPE_F32);
-        const bool quant = type == TTS_TYPE_Q4_K || type == TTS_TYPE_Q8_0 || type == TTS_TYPE_Q5_0 || type == TTS_TYPE_Q4_0;
+        const bool quant = type == TTS_TYPE_Q4_K || type == TTS_TYPE_Q6_K || type == TTS_TYPE_Q8_0 || type == TTS_TYPE_Q5_0 || type == TTS_TYPE_Q4_0;
         const bool ok = type == TTS_TYPE_F32 || (quant && (kind == 0 || kind == 3));
         if (!ok && p->type_err.empty())
             p->type_err = "gguf: tensor '" + p->w.gguf_name(name) + "' has type " + std::to_string(type) + ", which an Orpheus file cannot hold there";
         if (!ok) type = TTS_TYPE_F32;
+    } else if (p->cfg.weight_mix != 0 && type == TTS_TYPE_Q4_K && (kind == 0 || kind == 3)) {
+        // the synthetic model in the types the quantize tool's mix would give a file's tensors (heads quantized)
+        tts_quantize_params qp;
+        memset(&qp, 0, sizeof(qp));
+        qp.quantize_type = TTS_TYPE_Q4_K;
+        qp.quantize_output_heads = 1;
+        qp.mix = p->cfg.weight_mix;
+        const int32_t t = tts_gguf_tensor_out_type("orpheus", p->w.gguf_name(name).c_str(), p->cfg.n_layers, &qp);
+        if (t == TTS_TYPE_Q6_K) type = t;
     }
     weight_fill fill = kind == 1 ? weight_fill::uniform(0.1f, 1.0f) : weight_fill::matrix(kind == 3 ? 0.25f : 0.02f);
     if (kind == 4) {

@@ -141,9 +141,34 @@ void synth_q4_0(void * dst, int64_t rows, int64_t K, uint64_t seed, float std) {
     });
 }
 
+void synth_q6_K(void * dst, int64_t rows, int64_t K, uint64_t seed, float std) {
+    const int64_t nblk = rows * (K / QK_K);
+    block_q6_K * b = (block_q6_K *)dst;
+    const float d = std / 1221.f;  // U{-32..31} has std ~18.5, scales U{32..95} an rms of ~66
+    parallel_for((size_t)nblk, [&](size_t a, size_t e) {
+        for (size_t i = a; i < e; ++i) {
+            const uint64_t h0 = synth_hash(seed, i * 27);
+            b[i].d = fp32_to_fp16_host(d * (0.75f + 0.5f * u01(h0)));
+            for (int k = 0; k < 2; ++k) {
+                const uint64_t h = synth_hash(seed, i * 27 + 1 + k);
+                for (int j = 0; j < 8; ++j) b[i].scales[8 * k + j] = (int8_t)(32 + ((h >> (8 * j)) & 63));
+            }
+            for (int k = 0; k < 16; ++k) {
+                const uint64_t h = synth_hash(seed, i * 27 + 3 + k);
+                memcpy(b[i].ql + 8 * k, &h, 8);
+            }
+            for (int k = 0; k < 8; ++k) {
+                const uint64_t h = synth_hash(seed, i * 27 + 19 + k);
+                memcpy(b[i].qh + 8 * k, &h, 8);
+            }
+        }
+    });
+}
+
 void synth_fill(int type, void * dst, int64_t rows, int64_t K, uint64_t seed, float std) {
     switch (type) {
         case TTS_TYPE_Q4_K: synth_q4_K(dst, rows, K, seed, std); break;
+        case TTS_TYPE_Q6_K: synth_q6_K(dst, rows, K, seed, std); break;
         case TTS_TYPE_Q8_0: synth_q8_0(dst, rows, K, seed, std); break;
         case TTS_TYPE_Q5_0: synth_q5_0(dst, rows, K, seed, std); break;
         case TTS_TYPE_Q4_0: synth_q4_0(dst, rows, K, seed, std); break;

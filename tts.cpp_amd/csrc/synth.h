@@ -15,6 +15,7 @@ void synth_f16(uint16_t * dst, size_t n, uint64_t seed, float scale);
 // Valid Q4_K blocks with random nibbles / 6-bit scales / mins and d, dmin chosen so that the
 // dequantized weights are roughly zero-mean with std ~ `std`.
 void synth_q4_K(void * dst, int64_t rows, int64_t K, uint64_t seed, float std);
+void synth_q6_K(void * dst, int64_t rows, int64_t K, uint64_t seed, float std);
 void synth_q8_0(void * dst, int64_t rows, int64_t K, uint64_t seed, float std);
 void synth_q5_0(void * dst, int64_t rows, int64_t K, uint64_t seed, float std);
 void synth_q4_0(void * dst, int64_t rows, int64_t K, uint64_t seed, float std);

@@ -8,6 +8,7 @@ size_t tts_type_size(int type) {
         case TTS_TYPE_F32: return 4;
         case TTS_TYPE_F16: return 2;
         case TTS_TYPE_Q4_K: return sizeof(tts::block_q4_K);
+        case TTS_TYPE_Q6_K: return sizeof(tts::block_q6_K);
         case TTS_TYPE_Q4_0: return sizeof(tts::block_q4_0);
         case TTS_TYPE_Q5_0: return sizeof(tts::block_q5_0);
         case TTS_TYPE_Q8_0: return sizeof(tts::block_q8_0);
@@ -22,6 +23,7 @@ size_t tts_type_size(int type) {
 int64_t tts_blck_size(int type) {
     switch (type) {
         case TTS_TYPE_Q4_K:
+        case TTS_TYPE_Q6_K:
         case TTS_TYPE_Q8_K: return tts::QK_K;
         case TTS_TYPE_Q4_0: return tts::QK4_0;
         case TTS_TYPE_Q5_0: return tts::QK5_0;
@@ -37,6 +39,7 @@ const char * tts_type_name(int type) {
         case TTS_TYPE_F32: return "f32";
         case TTS_TYPE_F16: return "f16";
         case TTS_TYPE_Q4_K: return "q4_K";
+        case TTS_TYPE_Q6_K: return "q6_K";
         case TTS_TYPE_Q4_0: return "q4_0";
         case TTS_TYPE_Q5_0: return "q5_0";
         case TTS_TYPE_Q8_0: return "q8_0";

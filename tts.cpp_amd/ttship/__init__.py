@@ -13,7 +13,8 @@ REPO_ROOT = PKG_ROOT.parent
 LIB_PATH = PKG_ROOT / "lib" / "libtts_hip.so"
 
 # ggml type ids (include/tts_hip.h)
-F32, F16, Q4_0, Q5_0, Q8_0, Q4_K, Q8_K, I32 = 0, 1, 2, 6, 8, 12, 15, 26
+F32, F16, Q4_0, Q5_0, Q8_0, Q4_K, Q6_K, Q8_K, I32 = 0, 1, 2, 6, 8, 12, 14, 15, 26
+QUANT_MIX_Q4_K_M = 1  # TTS_QUANT_MIX_Q4_K_M
 PROF_ATTN = 39  # tts_hip_gemv_stats slot of the decode attention pair (TTS_PROF_ATTN)
 
 OPS = ["NONE", "DUP", "ADD", "SUB", "MUL", "DIV", "SQR", "SQRT", "SIN", "COS", "SUM_ROWS", "REPEAT",
@@ -33,8 +34,8 @@ ATTN_ONE_DEFAULT = 1  # backend default: the one-launch many-prompt decode atten
 GEMV_KR_TAIL_DEFAULT = 1  # backend default: the K-relay kernel's residual requested at entry, K = 1024 folded after one barrier
 ATTN_FUSED_ON = 128 # P >= 128 keys -> one 1024-thread launch (k_attn_fused; backend default 0 = off)
 
-TYPE_SIZE = {F32: 4, F16: 2, Q4_K: 144, Q8_0: 34, Q5_0: 22, Q4_0: 18, I32: 4}
-BLCK_SIZE = {F32: 1, F16: 1, Q4_K: 256, Q8_0: 32, Q5_0: 32, Q4_0: 32, I32: 1}
+TYPE_SIZE = {F32: 4, F16: 2, Q4_K: 144, Q6_K: 210, Q8_0: 34, Q5_0: 22, Q4_0: 18, I32: 4}
+BLCK_SIZE = {F32: 1, F16: 1, Q4_K: 256, Q6_K: 256, Q8_0: 32, Q5_0: 32, Q4_0: 32, I32: 1}
 
 
 class TtsTensor(ctypes.Structure):
@@ -187,7 +188,7 @@ class OrpheusConfig(ctypes.Structure):
         ("rope_low_freq_factor", ctypes.c_float),
         ("rope_high_freq_factor", ctypes.c_float),
         ("rope_original_ctx", ctypes.c_int32),
-        ("pad_", ctypes.c_int32),
+        ("weight_mix", ctypes.c_int32),
     ]
 
 
@@ -299,7 +300,8 @@ class QuantizeParams(ctypes.Structure):
     """tts_quantize_params (quantize_impl.h quantization_params without n_threads)."""
     _fields_ = [("quantize_type", ctypes.c_int32), ("quantize_output_heads", ctypes.c_int32),
                 ("quantize_text_embeddings", ctypes.c_int32), ("quantize_cross_attn_kv", ctypes.c_int32),
-                ("convert_dac_to_f16", ctypes.c_int32), ("convert_non_quantizable_to_f16", ctypes.c_int32)]
+                ("convert_dac_to_f16", ctypes.c_int32), ("convert_non_quantizable_to_f16", ctypes.c_int32),
+                ("mix", ctypes.c_int32)]
 
 
 # tts_quantize_rows_fn(ctx, type, x, dst, rows, K)
@@ -524,6 +526,7 @@ def lib():
         "tts_gguf_add_tensor": (ctypes.c_int, [vp, ctypes.c_char_p, i32, i32, ctypes.POINTER(i64), vp, u64]),
         "tts_gguf_writer_write": (ctypes.c_int, [vp, ctypes.c_char_p]),
         "tts_gguf_tensor_rule": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(QuantizeParams)]),
+        "tts_gguf_tensor_out_type": (ctypes.c_int32, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32, ctypes.POINTER(QuantizeParams)]),
         "tts_gguf_quantize": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(QuantizeParams), vp, vp]),
         "tts_hip_gguf_quantize": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(QuantizeParams)]),
         "tts_parler_config_from_gguf": (ctypes.c_int, [vp, ctypes.POINTER(ParlerConfig)]),
@@ -624,7 +627,7 @@ class HipBackend:
                 self.free(b)
 
     def quantize(self, wtype, x):
-        """Device quantization of f32 rows x [N][K] to ggml Q4_K / Q8_0 / Q5_0 / Q4_0 bytes (host array out)."""
+        """Device quantization of f32 rows x [N][K] to ggml Q4_K / Q6_K / Q8_0 / Q5_0 / Q4_0 bytes (host array out)."""
         import numpy as np
         x = np.ascontiguousarray(x, dtype=np.float32)
         N, K = x.shape
@@ -1539,6 +1542,12 @@ def gguf_tensor_rule(arch, name, params=None):
     """1 = quantize, 2 = convert to F16, 0 = copy (quantize_impl.cpp's is_quantizable / F16 rules)."""
     p = params or quantize_params()
     return lib().tts_gguf_tensor_rule(arch.encode() if arch else None, name.encode(), ctypes.byref(p))
+
+
+def gguf_tensor_out_type(arch, name, n_layers, params=None):
+    """The type the quantize tool gives a tensor of an F32 file of n_layers layers (F32 = copied); negative = refused."""
+    p = params or quantize_params()
+    return lib().tts_gguf_tensor_out_type(arch.encode() if arch else None, name.encode(), n_layers, ctypes.byref(p))
 
 
 def quantize_gguf(src, dst, params=None, backend=None, rows_fn=None):

@@ -391,6 +391,18 @@ enum tts_hip_option {
                                      API; costs the conv weights' size again as f32.  Same chunks, same MFMA order: bit-identical.
                                      0 = every workgroup rounds and scatters its slice itself (k_conv1d_f64).  The environment
                                      variable TTS_HIP_OPT_CONV_PACK sets the default */
+    TTS_HIP_OPT_CONVT_PACK = 56,  /* 1 (default) = unsplit conv_transpose_1d launches of the LDS-staged f64-MFMA kernel (stride 2, 4, 6,
+                                     8 or 10, kernel = 2 x stride) whose weight is a constant leaf stage it from a packed image in
+                                     the kernel's LDS order (k_convt_f64_img; the image table, its upkeep and its counters are
+                                     TTS_HIP_OPT_CONV_PACK's), and strides 6, 8 and 10 run eight waves of 16 channels each instead
+                                     of four of 32, so that two or more waves share a SIMD; costs the transposed convs' weights again
+                                     as f32.  Same chunks, same MFMA order: bit-identical.  0 = k_convt_f64_lds fetches and
+                                     transposes the slice itself.  The environment variable TTS_HIP_OPT_CONVT_PACK sets the default */
+    TTS_HIP_OPT_CONV_XREG = 57,   /* 1 (default) = the packed fused conv_1d kernel (k_conv1d_f64p) reads a lane's 16 entries of its
+                                     reduction-slot -> x-window table into registers once per workgroup, so that the x reads of
+                                     an MFMA batch no longer wait for table reads issued at the batch's head; same reads of the
+                                     same slots, same MFMA order: bit-identical.  0 = the table is read from LDS per batch.  The
+                                     environment variable TTS_HIP_OPT_CONV_XREG sets the default */
     TTS_HIP_OPT_COALESCE = 37,    /* 1 (default): while the process-wide coalescer is on (tts_hip_coalesce_enable), this
                                      backend's graph_compute of a one-prompt decode step may join the same step of other
                                      backends on the device as one coalesced launch (tts_hip_coalesce_stats); 0 = never */

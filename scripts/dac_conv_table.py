@@ -45,8 +45,10 @@ def main():
     for row in csv.DictReader(open(path)):
         if "k_conv1d_f64" not in row["Kernel_Name"]:
             continue
-        name = row["Kernel_Name"]  # k_conv1d_f64<W16, BIAS, RES, H32, MT>: MT = 3 is the 96-row tile
-        kind = "vfma" if "k_conv1d_f64v" in name else "mfma96" if name.split("(")[0].rstrip().endswith(", 3>") else "mfma64"
+        name = row["Kernel_Name"]  # k_conv1d_f64<W16, BIAS, RES, H32, MT>, k_conv1d_f64p<BIAS, RES, MT, XREG>: MT = 3 is the 96-row tile
+        targs = name.split("(")[0].rstrip().rstrip(">").split("<")[-1].split(", ")
+        mt = targs[2] if "k_conv1d_f64p" in name and len(targs) > 3 else targs[-1]
+        kind = "vfma" if "k_conv1d_f64v" in name else "mfma96" if mt == "3" else "mfma64"
         g = keys.get((kind, int(row["Grid_Size_X"]), int(row["Grid_Size_Y"])))
         dur = int(row["End_Timestamp"]) - int(row["Start_Timestamp"])
         if g is not None:
@@ -63,6 +65,30 @@ def main():
         fl = 2.0 * IC * OC * K * OL
         print(f"| {name} | {IC} | {OC} | {K} | {d} | {OL} | {len(v)} | {med / 1e3:.1f} | {fl / 1e9:.2f} | {fl / med / 1e3:.1f} | {100 * sum(v) / total:.1f} % |")
     print(f"\nunmatched conv1d launches: {other / 1e3:.1f} us of {total / 1e3:.1f} us")
+    convt_table(path, T)
+
+
+def convt_table(path, T):
+    """The transposed-conv launches (k_convt_f64_lds / k_convt_f64_img: 64-position x 32-channel workgroup tiles over
+    L + 1 polyphase positions) per (IC, OC, S), matched by their grid in workgroups."""
+    keys, c, L = {}, DIM, T
+    for b, r in enumerate(RATES):
+        keys[(L + 1 + 63) // 64, (c // 2 + 31) // 32] = (f"b{b + 1}.convt", c, c // 2, r, L)
+        c, L = c // 2, L * r
+    ns = collections.defaultdict(list)
+    for row in csv.DictReader(open(path)):
+        if "k_convt_f64" not in row["Kernel_Name"]:
+            continue
+        g = keys.get((int(row["Grid_Size_X"]) // int(row["Workgroup_Size_X"]), int(row["Grid_Size_Y"])))
+        if g is not None:
+            ns[g + (row["Kernel_Name"].split("(")[0].replace("void tts::", ""),)].append(int(row["End_Timestamp"]) - int(row["Start_Timestamp"]))
+    print("\n| transposed conv | kernel | IC | OC | S | L | launches | median us | GFLOP | TFLOP/s |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+    for (name, IC, OC, S, L, kern), v in sorted(ns.items()):
+        v.sort()
+        med = v[len(v) // 2]
+        fl = 2.0 * IC * OC * 2 * S * L
+        print(f"| {name} | `{kern}` | {IC} | {OC} | {S} | {L} | {len(v)} | {med / 1e3:.1f} | {fl / 1e9:.2f} | {fl / med / 1e3:.1f} |")
 
 
 if __name__ == "__main__":

@@ -197,6 +197,10 @@ tts_hip_backend_t tts_hip_backend_init(int device) {
         if (e[0] >= '0' && e[0] <= '2' && !e[1]) be->conv_vfma = e[0] - '0';
     if (const char * e = getenv("TTS_HIP_OPT_CONV_PACK"))
         if (e[0] >= '0' && e[0] <= '1' && !e[1]) be->conv_pack = e[0] - '0';
+    if (const char * e = getenv("TTS_HIP_OPT_CONVT_PACK"))
+        if (e[0] >= '0' && e[0] <= '1' && !e[1]) be->convt_pack = e[0] - '0';
+    if (const char * e = getenv("TTS_HIP_OPT_CONV_XREG"))
+        if (e[0] >= '0' && e[0] <= '1' && !e[1]) be->conv_xreg = e[0] - '0';
     be->conv_part_doubles = (size_t)8 << 20;  // 64 MiB of f64 partial sums
     TTS_HIP_CHECK(hipMalloc((void **)&be->conv_part, be->conv_part_doubles * sizeof(double)));
     be->lstm_floats = kLstmFloats;
@@ -861,6 +865,8 @@ extern "C" int tts_hip_set_option(tts_hip_backend_t be, int option, int value) {
         case TTS_HIP_OPT_CONV_VFMA: be->conv_vfma = value < 0 || value > 2 ? 1 : value; return 0;
         case TTS_HIP_OPT_CONV_TILE96: be->conv_tile96 = value != 0; return 0;
         case TTS_HIP_OPT_CONV_PACK: be->conv_pack = value != 0; return 0;
+        case TTS_HIP_OPT_CONVT_PACK: be->convt_pack = value != 0; return 0;
+        case TTS_HIP_OPT_CONV_XREG: be->conv_xreg = value != 0; return 0;
         case TTS_HIP_OPT_PROFILE_GEMV: be->profile_gemv = value != 0; return 0;
         case TTS_HIP_OPT_GRAPHS: be->use_graphs = value != 0; return 0;
         case TTS_HIP_OPT_CONV_F32ACC:

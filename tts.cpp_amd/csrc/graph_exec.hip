@@ -1522,6 +1522,26 @@ struct Planner {
     static const tts_tensor * through_view(const tts_tensor * t) { return t && t->op == TTS_OP_RESHAPE ? t->src[0] : t; }
     bool wr_hull = false;  // wr_lo / wr_hi computed: the hull of the memory this graph's nodes write
     const char *wr_lo = nullptr, *wr_hi = nullptr;
+    // A packed image (conv_pack_get) stands for a conv kernel only while nothing but the host API writes it: a
+    // leaf in a live buffer of its own allocation that no node of this graph writes.
+    // (A kernel outside the hull of everything the graph writes -- a weight buffer beside the compute arena
+    // -- needs no pass over the nodes: Kokoro's graphs have thousands.)
+    bool const_leaf(const tts_tensor * kern) {
+        if (kern->op != TTS_OP_NONE || (kern->flags & (TTS_FLAG_HOSTDATA | TTS_FLAG_OUTPUT)) || !buffer_lookup(kern->data, nullptr, nullptr)) return false;
+        if (!wr_hull) {
+            wr_hull = true;
+            for (int j = 0; j < n; ++j) {
+                if (is_view(nodes[j]->op) || !nodes[j]->data) continue;
+                const char * lo = (const char *)nodes[j]->data;
+                wr_lo = wr_lo ? std::min(wr_lo, lo) : lo;
+                wr_hi = std::max(wr_hi, lo + tbytes(nodes[j]));
+            }
+        }
+        if (wr_lo && (const char *)kern->data < wr_hi && (const char *)kern->data + tbytes(kern) > wr_lo)
+            for (int j = 0; j < n; ++j)
+                if (!is_view(nodes[j]->op) && nodes[j]->data && overlap(nodes[j], kern)) return false;
+        return true;
+    }
     void try_conv(int i) {
         const tts_tensor * col = nodes[i];
         const tts_tensor *kern = col->src[0], *x = col->src[1];
@@ -1623,23 +1643,7 @@ struct Planner {
         const size_t wb = tbytes(kern);
         if (xb >= 0x80000000u || wb >= 0x80000000u) return plan_reject("conv", 12);  // 32-bit buffer offsets
         a.x_bytes = (uint32_t)xb, a.w_bytes = (uint32_t)wb;
-        // a packed image (conv_pack_get) stands for the kernel only while nothing but the host API writes it: a
-        // leaf in a live buffer of its own allocation that no node of this graph writes
-        // (a kernel outside the hull of everything the graph writes -- a weight buffer beside the compute arena
-        // -- needs no pass over the nodes: Kokoro's graphs have thousands)
-        a.w_stable = kern->op == TTS_OP_NONE && !(kern->flags & (TTS_FLAG_HOSTDATA | TTS_FLAG_OUTPUT)) && buffer_lookup(kern->data, nullptr, nullptr);
-        if (a.w_stable && !wr_hull) {
-            wr_hull = true;
-            for (int j = 0; j < n; ++j) {
-                if (is_view(nodes[j]->op) || !nodes[j]->data) continue;
-                const char * lo = (const char *)nodes[j]->data;
-                wr_lo = wr_lo ? std::min(wr_lo, lo) : lo;
-                wr_hi = std::max(wr_hi, lo + tbytes(nodes[j]));
-            }
-        }
-        if (a.w_stable && wr_lo && (const char *)kern->data < wr_hi && (const char *)kern->data + wb > wr_lo)
-            for (int j = 0; a.w_stable && j < n; ++j)
-                if (!is_view(nodes[j]->op) && nodes[j]->data && overlap(nodes[j], kern)) a.w_stable = 0;
+        a.w_stable = const_leaf(kern);
         Item it;
         it.kind = Item::CONV;
         it.conv = a;
@@ -3005,23 +3009,29 @@ static bool capture_worthy(tts_hip_backend * be, tts_tensor * const * nodes, int
     return true;
 }
 
-// The packed kernel images a graph's fused convs will ask for (launch_conv1d_fused) are made on the compute
-// stream before the graph is recorded: an allocation and a launch that must not become part of the recording.
-// Graphs without an IM2COL (every decode step) cost one pass over the node list.
+// The packed kernel images a graph's fused convs (launch_conv1d_fused) and transposed convs
+// (launch_conv_transpose_1d) will ask for are made on the compute stream before the graph is recorded: an
+// allocation and a launch that must not become part of the recording.
+// Graphs without an IM2COL or a CONV_TRANSPOSE_1D (every decode step) cost one pass over the node list.
 namespace tts {
 static void plan_setup(Planner & pl, const tts_hip_backend * be);
 }
 static void conv_pack_prepare(tts_hip_backend * be, tts_tensor * const * nodes, int n_nodes) {
-    if (!be->conv_pack || !(be->fusion & TTS_FUSE_CONV)) return;
+    const bool conv = be->conv_pack && (be->fusion & TTS_FUSE_CONV), convt = be->convt_pack && be->fusion;
     bool any = false;
-    for (int i = 0; i < n_nodes && !any; ++i) any = nodes[i]->op == TTS_OP_IM2COL;
+    for (int i = 0; i < n_nodes && !any; ++i) any = (conv && nodes[i]->op == TTS_OP_IM2COL) || (convt && nodes[i]->op == TTS_OP_CONV_TRANSPOSE_1D);
     if (!any) return;
     Planner pl;
     plan_setup(pl, be);
     pl.build(nodes, n_nodes);
     for (const Item & it : pl.items) {
         ConvPackKey k;
-        if (it.kind == Item::CONV && conv1d_pack_key(be, it.conv, &k)) (void)conv_pack_get(be, k);
+        if (conv && it.kind == Item::CONV && conv1d_pack_key(be, it.conv, &k)) (void)conv_pack_get(be, k);
+    }
+    for (int i = 0; convt && i < n_nodes; ++i) {  // graph_compute_launches' rule for the transposed convs
+        ConvPackKey k;
+        if (pl.act[i] == 0 && nodes[i]->op == TTS_OP_CONV_TRANSPOSE_1D && !be->bat && convt_pack_key(be, nodes[i], pl.const_leaf(nodes[i]->src[0]), &k))
+            (void)conv_pack_get(be, k);
     }
 }
 
@@ -3310,7 +3320,11 @@ int graph_compute_launches(tts_hip_backend_t be, tts_tensor * const * nodes, int
             TTS_HIP_CHECK(hipStreamWaitEvent(be->stream, be->pf_join, 0));
             pf_pending = -1;
         }
-        const int st = a > 0 ? run_item(be, pl.items[a - 1], pl.items) : run_node(be, n);
+        int st = 0;
+        if (a > 0) st = run_item(be, pl.items[a - 1], pl.items);
+        else if (n->op == TTS_OP_CONV_TRANSPOSE_1D && be->fusion && be->convt_pack && !be->bat)  // the planner is built: it can prove the weight constant
+            launch_conv_transpose_1d(be, n, pl.const_leaf(n->src[0]));
+        else st = run_node(be, n);
         if (is_pf) {
             ++pf_next;
             pf_fork();

@@ -538,6 +538,8 @@ struct tts_hip_backend {
     int conv_vfma = 1;   // TTS_HIP_OPT_CONV_VFMA: 0 = never, 1 = convs of fewer than 8 output channels, 2 = wherever it applies
     int conv_tile96 = 1;  // TTS_HIP_OPT_CONV_TILE96: the 96-row tile of the fused conv_1d when OC % 96 == 0
     int conv_pack = 1;    // TTS_HIP_OPT_CONV_PACK: unsplit fused conv_1d launches stage the kernel from its packed image
+    int convt_pack = 1;   // TTS_HIP_OPT_CONVT_PACK: unsplit LDS conv_transpose_1d launches stage the weight from its packed image
+    int conv_xreg = 1;    // TTS_HIP_OPT_CONV_XREG: k_conv1d_f64p holds its r -> x-slot table in registers
     bool capturing = false;  // capture_into is recording: no allocation, no launch outside the recorded graph
     int conv_split = 1;  // TTS_HIP_OPT_CONV_SPLIT: 1 = split short convolutions to ~512 workgroups, N > 1 = to ~N, 0 = never
     int fusion = 0x3FFF;  // bitmask of TTS_FUSE_* patterns (all on)
@@ -663,7 +665,8 @@ void launch_snake(tts_hip_backend * be, const tts_tensor * dst, const tts_tensor
 void launch_lstm_finish(tts_hip_backend * be, const tts_tensor * final_out, const float * hist, int64_t Hd, int64_t T);
 bool audio_op_supported(const tts_tensor * n);
 int launch_audio_op(tts_hip_backend * be, const tts_tensor * n);
-void launch_conv_transpose_1d(tts_hip_backend * be, const tts_tensor * node);
+// w_stable: the planner proved the weight a constant leaf (Planner::const_leaf), so the launch may read its packed image
+void launch_conv_transpose_1d(tts_hip_backend * be, const tts_tensor * node, int w_stable = 0);
 // conv_1d chain (IM2COL -> MUL_MAT [-> ADD bias] [-> ADD residual]) as one implicit-GEMM kernel
 constexpr int CONV1D_MAX_R = 128;
 struct Conv1dArgs {
@@ -715,14 +718,21 @@ __host__ __device__ inline int64_t conv1d_pack_index(int nchunk, int oct, int rp
     const int lane = (r & 3) * 16 + (row & 15);
     return (int64_t)(ct * nchunk + chunk) * oct * rp + ((((row >> 4) * (rp >> 4) + (r >> 4)) * 64 + lane) * 4 + ((r >> 2) & 3));
 }
+// The packed image of a conv_transpose_1d weight [K = 2 S, OC, IC] for k_convt_f64_img: per (tile of 32 output
+// channels, chunk of 16 input channels) the 16 x K x 32 slice -- the weight's own f32 values (an F16 weight
+// converts exactly), zero past IC and past OC -- in the kernel's LDS order [tap][channel half][ic][16 channels].
+// One MFMA step's A read (tap, half; lanes kq = input channel, c16 = channel) covers 64 consecutive floats, and
+// a slice is a straight 16-byte-per-thread copy into LDS.  This function alone defines the layout.
+__host__ __device__ inline int convt_pack_index(int tap, int half, int icl, int c16) { return (((tap * 2 + half) * 16 + icl) * 16) + c16; }
 struct ConvPackKey {  // one image: the backend that owns it, the source bytes' layout, the tile geometry
     const tts_hip_backend * be;
     const void * w;
+    int kind = 0;  // 0: conv_1d (conv1d_pack_index), 1: conv_transpose_1d (convt_pack_index: oct 32, icc 16, rp 16 K)
     int w16, K, oct, icc, rp;
     int64_t IC, OC, wk, wic, woc;
     bool operator<(const ConvPackKey & o) const {
-        return std::tie(be, w, w16, K, oct, icc, rp, IC, OC, wk, wic, woc) <
-               std::tie(o.be, o.w, o.w16, o.K, o.oct, o.icc, o.rp, o.IC, o.OC, o.wk, o.wic, o.woc);
+        return std::tie(be, w, kind, w16, K, oct, icc, rp, IC, OC, wk, wic, woc) <
+               std::tie(o.be, o.w, o.kind, o.w16, o.K, o.oct, o.icc, o.rp, o.IC, o.OC, o.wk, o.wic, o.woc);
     }
     int nchunk() const { return (int)((IC + icc - 1) / icc); }
     int ntile() const { return (int)((OC + oct - 1) / oct); }
@@ -738,6 +748,8 @@ void conv_pack_written(tts_hip_backend * be, const void * p, size_t n);
 void conv_pack_freed(const tts_hip_backend * be, const void * p, size_t n);
 // The image launch_conv1d_fused will ask for (k_conv.hip), or false where this launch keeps k_conv1d_f64's staging.
 bool conv1d_pack_key(const tts_hip_backend * be, const Conv1dArgs & a, ConvPackKey * k);
+// The same for launch_conv_transpose_1d of `node` (w_stable as there): false where it keeps k_convt_f64_lds.
+bool convt_pack_key(const tts_hip_backend * be, const tts_tensor * node, int w_stable, ConvPackKey * k);
 // AdaIN (+ snake) per channel row: y[c][t] = snake((norm(x[c])[t] * (1 + g[c])...) -- see k_fused.hip
 struct AdainArgs {
     const float * x = nullptr;   // NORM input rows: x[c * xcs + t], t < T

@@ -535,9 +535,28 @@ __global__ __launch_bounds__(256) void k_conv1d_pack(ConvPackKey k, float * __re
     img[conv1d_pack_index(nchunk, k.oct, k.rp, ct, chunk, row, r)] = v;
 }
 
+// The packed image of a conv_transpose_1d weight (convt_pack_index, hip_internal.h): thread e owns element
+// (slice, tap, channel half, ic, channel) of the image and reads it from the source through its strides.
+__global__ __launch_bounds__(256) void k_convt_pack(ConvPackKey k, float * __restrict__ img, int nchunk, int64_t n) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    const int per = 512 * k.K;  // 16 input channels x K taps x 32 channels
+    const int slice = (int)(e / per), w = (int)(e - (int64_t)slice * per);
+    const int ct = slice / nchunk, chunk = slice - ct * nchunk;
+    const int c16 = w & 15, icl = (w >> 4) & 15, half = (w >> 8) & 1, tap = w >> 9;
+    const int64_t oc = (int64_t)ct * 32 + half * 16 + c16, ic = (int64_t)chunk * 16 + icl;
+    float v = 0.f;
+    if (ic < k.IC && oc < k.OC) {
+        const int64_t o = oc * k.woc + (int64_t)tap * k.wk + ic * k.wic;
+        v = k.w16 ? __half2float(((const __half *)k.w)[o]) : ((const float *)k.w)[o];
+    }
+    img[(int64_t)slice * per + convt_pack_index(tap, half, icl, c16)] = v;
+}
+
 void launch_conv1d_pack(hipStream_t stream, const ConvPackKey & k, float * img) {
     const int64_t n = (int64_t)k.floats();
-    hipLaunchKernelGGL(k_conv1d_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, k, img, k.nchunk(), n);
+    if (k.kind == 1) hipLaunchKernelGGL(k_convt_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, k, img, k.nchunk(), n);
+    else hipLaunchKernelGGL(k_conv1d_pack,dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, k, img, k.nchunk(), n);
     TTS_HIP_CHECK(hipGetLastError());
 }
 
@@ -546,7 +565,8 @@ void launch_conv1d_pack(hipStream_t stream, const ConvPackKey & k, float * img) 
 // reads a lane's A operands of four steps as one 16-byte LDS read.  The x window is staged as before, but
 // only the ceil(icc * xw / 256) elements per thread the chunk has.  Chunks, the reduction index r of every
 // MFMA step and its k slot are k_conv1d_f64's, so every output's f64 sum -- and the result -- is the same.
-template <bool BIAS, bool RES, int MT>
+// XREG (TTS_HIP_OPT_CONV_XREG): the r -> x-slot table is held in registers instead of read from LDS per batch.
+template <bool BIAS, bool RES, int MT, bool XREG>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 1 : 2))) void k_conv1d_f64p(Conv1dArgs a) {
     constexpr int OCT = 32 * MT, WQ = 2 * MT;  // workgroup rows, 16-byte kernel-slice pieces per thread at Rp = 64
     extern __shared__ float sm[];
@@ -568,6 +588,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 1
     __syncthreads();
     const int wr0 = (wave >> 1) * 16 * MT, wc0 = (wave & 1) * 32;
     const bool wave_live = oc0 + wr0 < a.OC && ol0 + wc0 < a.OL;  // wave-uniform
+    // XREG: the lane's table entries r = 32 b + 4 u + kq (Rp <= 64: 16 of them) read once into registers, so a
+    // batch's x reads no longer wait for table reads issued at its head
+    int xoa[2][8];
+    if (XREG) {
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int u = 0; u < 8; ++u) xoa[b][u] = 32 * b < Rp ? xoff[32 * b + 4 * u + kq] : zslot;
+    }
     f64x4_t acc[MT][2] = {};
     const int64_t base = ol0 * s - a.p;
     const int EX = icc * xw;
@@ -618,10 +647,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 1
             __syncthreads();
             continue;
         }
-        for (int r0 = 0; r0 < Rp; r0 += 32) {
-            int xo[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) xo[u] = xoff[r0 + 4 * u + kq];
+        auto batch = [&](int r0, const int (&xo)[8]) {  // the 8 MFMA steps of reduction slots r0 .. r0 + 31
             float af[8][MT], bf[8][2];
 #pragma unroll
             for (int h = 0; h < 2; ++h)
@@ -645,6 +671,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 1
 #pragma unroll
                     for (int tj = 0; tj < 2; ++tj)
                         acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)af[u][ti], (double)bf[u][tj], acc[ti][tj], 0, 0, 0);
+        };
+        if (XREG) {
+            batch(0, xoa[0]);
+            if (Rp == 64) batch(32, xoa[1]);
+        } else {
+            for (int r0 = 0; r0 < Rp; r0 += 32) {
+                int xo[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) xo[u] = xoff[r0 + 4 * u + kq];
+                batch(r0, xo);
+            }
         }
         __syncthreads();
     }
@@ -771,8 +808,8 @@ bool conv1d_pack_key(const tts_hip_backend * be, const Conv1dArgs & a0, ConvPack
     int vxw = 0, vicc = 0;
     size_t vlds = 0;
     if (be->conv_vfma && (be->conv_vfma == 2 || a.OC < 8) && conv1d_vfma_geometry(a, &vxw, &vicc, &vlds)) return false;
-    k->be = be, k->w = a.w, k->w16 = a.w16, k->K = a.K;
-    k->oct = be->conv_tile96 && a.OC % 96 == 0 ? 96 : 64;
+    k->be = be, k->w = a.w, k->kind = 0, k->w16 = a.w16, k->K = a.K;
+    k->oct =be->conv_tile96 && a.OC % 96 == 0 ? 96 : 64;
     k->icc = a.icc, k->rp = (a.icc * a.K + 31) & ~31;
     k->IC = a.IC, k->OC = a.OC, k->wk = a.wk, k->wic = a.wic, k->woc = a.woc;
     return true;
@@ -829,16 +866,19 @@ void launch_conv1d_fused(tts_hip_backend * be, Conv1dArgs a) {
         const size_t plds = ((size_t)pk.oct * pk.rp + (size_t)a.icc * a.xw + 1) * 4;
         grid.y = (unsigned)pk.ntile();
         const int psel = (pk.oct == 96 ? 4 : 0) | (a.bias ? 2 : 0) | (a.res ? 1 : 0);
-        switch (psel) {
-            case 0: hipLaunchKernelGGL((k_conv1d_f64p<false, false, 2>), grid, dim3(256), plds, be->stream, a); break;
-            case 1: hipLaunchKernelGGL((k_conv1d_f64p<false, true, 2>), grid, dim3(256), plds, be->stream, a); break;
-            case 2: hipLaunchKernelGGL((k_conv1d_f64p<true, false, 2>), grid, dim3(256), plds, be->stream, a); break;
-            case 3: hipLaunchKernelGGL((k_conv1d_f64p<true, true, 2>), grid, dim3(256), plds, be->stream, a); break;
-            case 4: hipLaunchKernelGGL((k_conv1d_f64p<false, false, 3>), grid, dim3(256), plds, be->stream, a); break;
-            case 5: hipLaunchKernelGGL((k_conv1d_f64p<false, true, 3>), grid, dim3(256), plds, be->stream, a); break;
-            case 6: hipLaunchKernelGGL((k_conv1d_f64p<true, false, 3>), grid, dim3(256), plds, be->stream, a); break;
-            default: hipLaunchKernelGGL((k_conv1d_f64p<true, true, 3>), grid, dim3(256), plds, be->stream, a); break;
-        }
+#define TTS_CONV1D_PACKED(XREG)                                                                                                     \
+    switch (psel) {                                                                                                                  \
+        case 0: hipLaunchKernelGGL((k_conv1d_f64p<false, false, 2, XREG>), grid, dim3(256), plds, be->stream, a); break;             \
+        case 1: hipLaunchKernelGGL((k_conv1d_f64p<false, true, 2, XREG>), grid, dim3(256), plds, be->stream, a); break;              \
+        case 2: hipLaunchKernelGGL((k_conv1d_f64p<true, false, 2, XREG>), grid, dim3(256), plds, be->stream, a); break;              \
+        case 3: hipLaunchKernelGGL((k_conv1d_f64p<true, true, 2, XREG>), grid, dim3(256), plds, be->stream, a); break;               \
+        case 4: hipLaunchKernelGGL((k_conv1d_f64p<false, false, 3, XREG>), grid, dim3(256), plds, be->stream, a); break;             \
+        case 5: hipLaunchKernelGGL((k_conv1d_f64p<false, true, 3, XREG>), grid, dim3(256), plds, be->stream, a); break;              \
+        case 6: hipLaunchKernelGGL((k_conv1d_f64p<true, false, 3, XREG>), grid, dim3(256), plds, be->stream, a); break;              \
+        default: hipLaunchKernelGGL((k_conv1d_f64p<true, true, 3, XREG>), grid, dim3(256), plds, be->stream, a); break;              \
+    }
+        if (be->conv_xreg) { TTS_CONV1D_PACKED(true) } else { TTS_CONV1D_PACKED(false) }
+#undef TTS_CONV1D_PACKED
     } else if (nz == 1 && be->conv_acc_mode != 2 && be->conv_tile96 && a.OC % 96 == 0) {
         grid.y = (unsigned)(a.OC / 96);
         lds += 32 * (size_t)a.rs * 4;  // 96 kernel rows instead of 64 (at most 41 KB in all)
@@ -1069,7 +1109,115 @@ __global__ __launch_bounds__(256) void k_convt_f64_lds(TD y, TD x, TD w, int p, 
     }
 }
 
-void launch_conv_transpose_1d(tts_hip_backend * be, const tts_tensor * node) {
+// k_convt_f64_lds (unsplit) with the weight slice staged from the packed image (convt_pack_index): a chunk's
+// slice is 128 K / threads 16-byte loads and LDS writes per thread, fetched one chunk ahead, with no
+// transposition and no padding -- one MFMA step's A read covers 64 consecutive LDS floats.  NWV = 8 (the wide
+// strides): eight waves, wave = (16 positions, one half of the 32 channels), so a lane holds 4 S accumulators
+// instead of 8 S, the kernel fits 128 registers and a SIMD holds two to four waves instead of one: one wave's
+// staging runs beside another's MFMAs.  NWV = 4: k_convt_f64_lds's four waves of both halves.  Chunks, the
+// four input channels of every MFMA and the order (ic quad kk ascending, tap group j = 0 then 1) are
+// k_convt_f64_lds's, so every output's f64 sum -- and the result -- is the same.
+template <int S, bool W16, int NWV>
+__global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(NWV == 8 ? (S <= 8 ? 4 : 2) : 1))) void k_convt_f64_img(TD y, TD x, uint32_t x_bytes, const float * __restrict__ wimg, int OC, int IC, int p) {
+    constexpr int JM = 2, K = 2 * S, NT = 64 * NWV, HN = NWV == 8 ? 1 : 2;
+    constexpr int QT = 64, OCT = 32, ICC = 16, XW = QT + JM - 1, XWP = 80;  // XWP: k_convt_f64_lds's padded x row
+    constexpr int NX = ICC * XW, NW4 = ICC * K * OCT / 4;
+    constexpr int XR = (NX + NT - 1) / NT, WR = NW4 / NT;
+    static_assert(NW4 % NT == 0, "whole 16-byte pieces per thread");
+    __shared__ float xs[ICC][XWP];
+    __shared__ f32x4_t ws4[NW4];
+    const float * ws = (const float *)ws4;
+    const int tid = threadIdx.x, lane = tid & 63, qw = (tid >> 6) & 3, h0 = NWV == 8 ? tid >> 8 : 0;
+    const int c16 = lane & 15, kq = lane >> 4;
+    const int64_t L = x.ne[0], OL = y.ne[0];
+    const int64_t q0 = (int64_t)blockIdx.x * QT;
+    const int oc0 = blockIdx.y * OCT;
+    f64x4_t acc[S][HN];
+#pragma unroll
+    for (int r = 0; r < S; ++r)
+#pragma unroll
+        for (int h = 0; h < HN; ++h) acc[r][h] = (f64x4_t){0.0, 0.0, 0.0, 0.0};
+    const int nchunk = (IC + ICC - 1) / ICC;
+    const f32x4_t * wp = (const f32x4_t *)wimg + (int64_t)blockIdx.y * nchunk * NW4 + tid;  // this thread's pieces of chunk 0
+    // the x slice through a buffer descriptor, as k_conv1d_f64p: one 32-bit offset per element, fixed for the
+    // launch but for the chunk's channel base; positions outside [0, L) and channels past IC read as 0
+    const uint32_t OOB = 0x80000000u;
+    const auto xd = __builtin_amdgcn_make_buffer_rsrc(x.data, 0, x_bytes, 0x00020000);
+    uint32_t xrel[XR];
+#pragma unroll
+    for (int u = 0; u < XR; ++u) {
+        const int t = tid + NT * u;
+        const int ic = t / XW, qq = t - ic * XW;
+        const int64_t pos = q0 - (JM - 1) + qq;
+        xrel[u] = t < NX && pos >= 0 && pos < L ? (uint32_t)(pos * x.nb[0] + (int64_t)ic * x.nb[1]) : OOB;
+    }
+    float xr[XR];
+    f32x4_t wr[WR];
+    auto fetch = [&](int ic0) {
+        const int nic = min(ICC, IC - ic0);
+        const uint32_t xc = (uint32_t)((int64_t)ic0 * x.nb[1]);
+#pragma unroll
+        for (int u = 0; u < XR; ++u) {
+            const uint32_t off = (xrel[u] == OOB || tid + NT * u >= nic * XW) ? OOB : xrel[u] + xc;
+            xr[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xd, off, 0, 0));
+            if (W16) xr[u] = __half2float(__float2half_rn(xr[u]));  // F16 kernel: the input rounded to f16
+        }
+#pragma unroll
+        for (int u = 0; u < WR; ++u) wr[u] = wp[NT * u];
+        wp += NW4;
+    };
+    fetch(0);
+    for (int ic0 = 0; ic0 < IC; ic0 += ICC) {
+#pragma unroll
+        for (int u = 0; u < XR; ++u) {
+            const int t = tid + NT * u;
+            if (t < NX) xs[t / XW][t % XW] = xr[u];
+        }
+#pragma unroll
+        for (int u = 0; u < WR; ++u) ws4[tid + NT * u] = wr[u];
+        __syncthreads();
+        if (ic0 + ICC < IC) fetch(ic0 + ICC);
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            const int icl = 4 * kk + kq;
+            float bx[JM], aw[JM][S][HN];
+#pragma unroll
+            for (int j = 0; j < JM; ++j) {
+                bx[j] = xs[icl][qw * 16 + c16 + (JM - 1) - j];
+#pragma unroll
+                for (int r = 0; r < S; ++r)
+#pragma unroll
+                    for (int h = 0; h < HN; ++h) aw[j][r][h] = ws[convt_pack_index(r + S * j, h0 + h, icl, c16)];
+            }
+#pragma unroll
+            for (int j = 0; j < JM; ++j) {
+                const double bv = (double)bx[j];
+#pragma unroll
+                for (int r = 0; r < S; ++r)
+#pragma unroll
+                    for (int h = 0; h < HN; ++h) acc[r][h] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)aw[j][r][h], bv, acc[r][h], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+    const int64_t q = q0 + qw * 16 + c16;
+#pragma unroll
+    for (int r = 0; r < S; ++r) {
+        const int64_t o = q * S + r - p;
+        if (o < 0 || o >= OL) continue;
+#pragma unroll
+        for (int h = 0; h < HN; ++h)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int oc = oc0 + (h0 + h) * 16 + kq + 4 * e;
+                if (oc < OC) *(float *)(y.data + o * y.nb[0] + (int64_t)oc * y.nb[1]) = (float)acc[r][h][e];
+            }
+    }
+}
+
+// launch_conv_transpose_1d's LDS-kernel rule and geometry: the position x channel grid, and over how many
+// input-channel splits (nz, icps channels each) a short sequence goes.  Shapes and options only.
+static bool convt_lds_geometry(const tts_hip_backend * be, const tts_tensor * node, dim3 * grid, int * nz, int * icps) {
     const tts_tensor * w = node->src[0];
     const tts_tensor * x = node->src[1];
     const int s = node->op_params[0], p = node->op_params[1], d = node->op_params[2], g = node->op_params[4];
@@ -1077,19 +1225,67 @@ void launch_conv_transpose_1d(tts_hip_backend * be, const tts_tensor * node) {
     const bool w16 = w->type == TTS_TYPE_F16;
     const size_t wal = w16 ? 8 : 16;
     const bool wvec = w->nb[0] == (w16 ? 2u : 4u) && w->nb[1] % wal == 0 && w->nb[2] % wal == 0 && ((uintptr_t)w->data % 16) == 0;
-    if (d == 1 && g == 1 && w->ne[1] >= 16 && x->ne[1] >= 16 && (s == 2 || s == 4 || s == 6 || s == 8 || s == 10) && w->ne[0] == 2 * s && wvec &&
-        be->convt_lds && node->nb[0] == 4) {
-        const int64_t nq = (node->ne[0] + p) / s + 1;
-        dim3 grid((unsigned)((nq + 63) / 64), (unsigned)((w->ne[1] + 31) / 32));
+    if (!(d == 1 && g == 1 && w->ne[1] >= 16 && x->ne[1] >= 16 && (s == 2 || s == 4 || s == 6 || s == 8 || s == 10) && w->ne[0] == 2 * s && wvec &&
+          be->convt_lds && node->nb[0] == 4))
+        return false;
+    const int64_t nq = (node->ne[0] + p) / s + 1;
+    *grid = dim3((unsigned)((nq + 63) / 64), (unsigned)((w->ne[1] + 31) / 32));
+    // short sequences: split the input channels (chunks of 16) over extra workgroups
+    const int64_t IC = x->ne[1], OL = node->ne[0], OC = node->ne[1];
+    const int64_t nchunk = (IC + 15) / 16;
+    *nz = split_count(be, (int64_t)grid->x * grid->y, nchunk, 2, OL * OC);
+    *icps = *nz > 1 ? (int)(((nchunk + *nz - 1) / *nz) * 16) : 0;
+    grid->z = *nz > 1 ? (unsigned)((IC + *icps - 1) / *icps) : 1u;
+    return true;
+}
+
+static size_t convt_x_bytes(const tts_tensor * x) { return (size_t)((x->ne[0] - 1) * x->nb[0] + (x->ne[1] - 1) * x->nb[1]) + 4; }
+
+bool convt_pack_key(const tts_hip_backend * be, const tts_tensor * node, int w_stable, ConvPackKey * k) {
+    if (!be->convt_pack || !w_stable) return false;
+    dim3 grid;
+    int nz = 1, icps = 0;
+    if (!convt_lds_geometry(be, node, &grid, &nz, &icps) || nz > 1) return false;
+    if (convt_x_bytes(node->src[1]) >= 0x80000000u) return false;  // 32-bit buffer offsets
+    const tts_tensor * w = node->src[0];
+    const int64_t es = w->type == TTS_TYPE_F16 ? 2 : 4;
+    k->be = be, k->w = w->data, k->kind = 1, k->w16 = w->type == TTS_TYPE_F16, k->K = (int)w->ne[0];
+    k->oct = 32, k->icc = 16, k->rp = 16 * k->K;
+    k->IC = w->ne[2], k->OC = w->ne[1];
+    k->wk = (int64_t)w->nb[0] / es, k->woc = (int64_t)w->nb[1] / es, k->wic = (int64_t)w->nb[2] / es;
+    return true;
+}
+
+void launch_conv_transpose_1d(tts_hip_backend * be, const tts_tensor * node, int w_stable) {
+    const tts_tensor * w = node->src[0];
+    const tts_tensor * x = node->src[1];
+    const int s = node->op_params[0], p = node->op_params[1], d = node->op_params[2], g = node->op_params[4];
+    const bool w16 = w->type == TTS_TYPE_F16;
+    dim3 grid;
+    int nz = 1, icps = 0;
+    if (convt_lds_geometry(be, node, &grid, &nz, &icps)) {
         const TD Y = make_td(node), X = make_td(x), W = make_td(w);
-        // short sequences: split the input channels (chunks of 16) over extra workgroups
-        const int64_t IC = x->ne[1], OL = node->ne[0], OC = node->ne[1];
-        const int64_t nchunk = (IC + 15) / 16;
-        const int nz = split_count(be, (int64_t)grid.x * grid.y, nchunk, 2, OL * OC);
-        const int icps = nz > 1 ? (int)(((nchunk + nz - 1) / nz) * 16) : 0;
+        const int64_t OL = node->ne[0], OC = node->ne[1];
         double * part = nz > 1 ? be->conv_part : nullptr;
-        grid.z = nz > 1 ? (unsigned)((IC + icps - 1) / icps) : 1u;
-#define TTS_CONVT_LDS(SS)                                                                                       \
+        // TTS_HIP_OPT_CONVT_PACK: an unsplit launch whose weight is a constant leaf stages it from the packed image
+        ConvPackKey pk;
+        if (const float * img = convt_pack_key(be, node, w_stable, &pk) ? conv_pack_get(be, pk) : nullptr) {
+            const uint32_t xb = (uint32_t)convt_x_bytes(x);
+#define TTS_CONVT_IMG(SS, NWV)                                                                                                              \
+    do {                                                                                                                                    \
+        if (w16) hipLaunchKernelGGL((k_convt_f64_img<SS, true, NWV>), grid, dim3(64 * NWV), 0, be->stream, Y, X, xb, img, (int)OC, (int)x->ne[1], p);  \
+        else hipLaunchKernelGGL((k_convt_f64_img<SS, false, NWV>), grid, dim3(64 * NWV), 0, be->stream, Y, X, xb, img, (int)OC, (int)x->ne[1], p);     \
+    } while (0)
+            if (s == 2) TTS_CONVT_IMG(2, 4);
+            else if (s == 4) TTS_CONVT_IMG(4, 4);
+            else if (s == 6) TTS_CONVT_IMG(6, 8);
+            else if (s == 8) TTS_CONVT_IMG(8, 8);
+            else TTS_CONVT_IMG(10, 8);
+#undef TTS_CONVT_IMG
+            TTS_HIP_CHECK(hipGetLastError());
+            return;
+        }
+#define TTS_CONVT_LDS(SS)                                                                                      \
     do {                                                                                                        \
         if (w16) hipLaunchKernelGGL((k_convt_f64_lds<SS, true>), grid, dim3(256), 0, be->stream, Y, X, W, p, part, icps);  \
         else hipLaunchKernelGGL((k_convt_f64_lds<SS, false>), grid, dim3(256), 0, be->stream, Y, X, W, p, part, icps);     \
@@ -1106,13 +1302,13 @@ void launch_conv_transpose_1d(tts_hip_backend * be, const tts_tensor * node) {
     }
     if (d == 1 && g == 1 && w->ne[1] >= 16 && x->ne[1] >= 16) {
         const int64_t nq = (node->ne[0] + p) / s + 1;  // q with q*s + rr - p < OL for some rr
-        const dim3 grid((unsigned)((nq + 15) / 16), (unsigned)((w->ne[1] + 15) / 16), (unsigned)s);
-        hipLaunchKernelGGL(k_conv_transpose_1d_mfma, grid, dim3(64), 0, be->stream, make_td(node), make_td(x), make_td(w), s, p);
+        const dim3 mgrid((unsigned)((nq + 15) / 16), (unsigned)((w->ne[1] + 15) / 16), (unsigned)s);
+        hipLaunchKernelGGL(k_conv_transpose_1d_mfma, mgrid, dim3(64), 0, be->stream, make_td(node), make_td(x), make_td(w), s, p);
         TTS_HIP_CHECK(hipGetLastError());
         return;
     }
-    const dim3 grid((unsigned)((node->ne[0] + 255) / 256), (unsigned)node->ne[1]);
-    hipLaunchKernelGGL(k_conv_transpose_1d, grid, dim3(256), 0, be->stream, make_td(node), make_td(x), make_td(w), node->op_params[0],
+    const dim3 vgrid((unsigned)((node->ne[0] + 255) / 256), (unsigned)node->ne[1]);
+    hipLaunchKernelGGL(k_conv_transpose_1d, vgrid, dim3(256), 0, be->stream, make_td(node), make_td(x), make_td(w), node->op_params[0],
                        node->op_params[1], node->op_params[2], node->op_params[4]);
     TTS_HIP_CHECK(hipGetLastError());
 }

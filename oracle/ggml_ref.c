@@ -734,16 +734,7 @@ static void op_dup(tts_tensor * dst, int ith, int nth) {
 
 /* ggml_compute_forward_cpy: cpy(a, b) writes a into b; dst is a view of b. */
 static void op_cpy(tts_tensor * dst, int ith, int nth) {
-    const tts_tensor * src = dst->src[0];
-    const int64_t n = nelements(src);
-    const int64_t dr = (n + nth - 1) / nth;
-    const int64_t k0 = dr * ith, k1 = MIN(k0 + dr, n);
-    int64_t is[4], id[4];
-    for (int64_t k = k0; k < k1; ++k) {
-        unravel(k, src->ne, is);
-        unravel(k, dst->ne, id);
-        store_elem(dst, id[0], id[1], id[2], id[3], load_elem(src, is[0], is[1], is[2], is[3]));
-    }
+    op_dup(dst, ith, nth); /* the same element walk; I32 -> I32 moves integers there */
 }
 
 /* ggml_compute_forward_{add,sub,mul,div}_f32 with ggml_can_repeat broadcasting of src1. */
@@ -1073,6 +1064,7 @@ static void op_concat(tts_tensor * dst, int ith, int nth) {
     const int dim = dst->op_params[0];
     int64_t o[4] = {0, 0, 0, 0};
     o[dim] = a->ne[dim];
+    const int i32 = dst->type == TTS_TYPE_I32 && a->type == TTS_TYPE_I32 && b->type == TTS_TYPE_I32; /* moved as integers */
     const int64_t nr = nrows(dst);
     const int64_t dr = (nr + nth - 1) / nth;
     const int64_t r0 = dr * ith, r1 = MIN(r0 + dr, nr);
@@ -1081,10 +1073,11 @@ static void op_concat(tts_tensor * dst, int ith, int nth) {
         const int64_t i2 = (r - i3 * dst->ne[2] * dst->ne[1]) / dst->ne[1];
         const int64_t i1 = r - i3 * dst->ne[2] * dst->ne[1] - i2 * dst->ne[1];
         for (int64_t i0 = 0; i0 < dst->ne[0]; ++i0) {
-            float v;
-            if (i0 < a->ne[0] && i1 < a->ne[1] && i2 < a->ne[2] && i3 < a->ne[3]) v = load_elem(a, i0, i1, i2, i3);
-            else v = load_elem(b, i0 - o[0], i1 - o[1], i2 - o[2], i3 - o[3]);
-            store_elem(dst, i0, i1, i2, i3, v);
+            const int first = i0 < a->ne[0] && i1 < a->ne[1] && i2 < a->ne[2] && i3 < a->ne[3];
+            const tts_tensor * s = first ? a : b;
+            const int64_t j0 = first ? i0 : i0 - o[0], j1 = first ? i1 : i1 - o[1], j2 = first ? i2 : i2 - o[2], j3 = first ? i3 : i3 - o[3];
+            if (i32) *(int32_t *)PF(dst, i0, i1, i2, i3) = *(const int32_t *)PF(s, j0, j1, j2, j3);
+            else store_elem(dst, i0, i1, i2, i3, load_elem(s, j0, j1, j2, j3));
         }
     }
 }
@@ -1099,20 +1092,24 @@ static void op_sum_rows(tts_tensor * dst, int ith, int nth) {
         const int64_t i1 = r - i3 * a->ne[2] * a->ne[1] - i2 * a->ne[1];
         ggml_float s = 0.0;
         for (int64_t i0 = 0; i0 < a->ne[0]; ++i0) s += (ggml_float)load_elem(a, i0, i1, i2, i3);
-        *PF(dst, 0, i1, i2, i3) = (float)s;
+        store_elem(dst, 0, i1, i2, i3, (float)s);
     }
 }
 
 /* ggml_compute_forward_repeat_f32: dst[i] = src[i mod ne_src]. */
 static void op_repeat(tts_tensor * dst, int ith, int nth) {
     const tts_tensor * a = dst->src[0];
+    const int i32 = dst->type == TTS_TYPE_I32 && a->type == TTS_TYPE_I32; /* ids and positions move as integers */
     const int64_t nr = nrows(dst);
     for (int64_t r = ith; r < nr; r += nth) {
         const int64_t i3 = r / (dst->ne[2] * dst->ne[1]);
         const int64_t i2 = (r - i3 * dst->ne[2] * dst->ne[1]) / dst->ne[1];
         const int64_t i1 = r - i3 * dst->ne[2] * dst->ne[1] - i2 * dst->ne[1];
-        for (int64_t i0 = 0; i0 < dst->ne[0]; ++i0)
-            store_elem(dst, i0, i1, i2, i3, load_elem(a, i0 % a->ne[0], i1 % a->ne[1], i2 % a->ne[2], i3 % a->ne[3]));
+        for (int64_t i0 = 0; i0 < dst->ne[0]; ++i0) {
+            const int64_t j0 = i0 % a->ne[0], j1 = i1 % a->ne[1], j2 = i2 % a->ne[2], j3 = i3 % a->ne[3];
+            if (i32) *(int32_t *)PF(dst, i0, i1, i2, i3) = *(const int32_t *)PF(a, j0, j1, j2, j3);
+            else store_elem(dst, i0, i1, i2, i3, load_elem(a, j0, j1, j2, j3));
+        }
     }
 }
 
@@ -1135,7 +1132,7 @@ static void op_rope(tts_tensor * dst, int ith, int nth) {
         for (int64_t i2 = 0; i2 < a->ne[2]; i2++) {
             const int64_t p = ((const int32_t *)pos->data)[i2];
             float theta = (float)p;
-            for (int64_t i0 = 0; i0 < a->ne[0]; i0 += 2) {
+            for (int64_t i0 = 0; i0 < n_dims; i0 += 2) { /* freq_factors holds n_dims / 2 entries */
                 const float f = ff ? ((const float *)ff->data)[i0 / 2] : 1.0f;
                 const float th = freq_scale * (theta / f);
                 cache[i0 + 0] = ref_cosf(th) * attn_factor;

@@ -72,8 +72,8 @@ class Graph:
         if on is not None:
             self.place(t, *on)
         else:
-            n = int(np.prod(ne)) * ttship.TYPE_SIZE[typ] // ttship.BLCK_SIZE[typ] if nb is None else None
-            buf = np.zeros(max(n or 0, 1) + 256, dtype=np.uint8)
+            n = int(np.prod(ne)) * ttship.TYPE_SIZE[typ] // ttship.BLCK_SIZE[typ] if nb is None else self.span(t)
+            buf = np.zeros(max(n, 1) + 256, dtype=np.uint8)
             self.arrays[id(t)] = buf
             t.data = buf.ctypes.data
         self.insert(t, at)

@@ -803,6 +803,21 @@ int tts_hip_weight_get(tts_hip_backend_t be, const tts_tensor * t, void * dst) {
 }
 
 static bool is_f32(const tts_tensor * t) { return t && t->type == TTS_TYPE_F32; }
+// what td_load / td_store convert through float: the element types of the arithmetic ops
+static bool is_fp(const tts_tensor * t) { return t && (t->type == TTS_TYPE_F32 || t->type == TTS_TYPE_F16); }
+// a row of floats the row kernels index through `float *` (any nb[1..3])
+static bool is_f32_rows(const tts_tensor * t) { return is_f32(t) && t->nb[0] == 4; }
+static bool is_dense(const tts_tensor * t) {
+    const size_t es = tts_type_size(t->type);
+    return t->nb[0] == es && t->nb[1] == es * (size_t)t->ne[0] && t->nb[2] == t->nb[1] * (size_t)t->ne[1] &&
+           t->nb[3] == t->nb[2] * (size_t)t->ne[2];
+}
+// CONCAT / REPEAT move values, so I32 passes whole when every operand is I32; F32 and F16 mix freely
+static bool movable(const tts_tensor * d, const tts_tensor * a, const tts_tensor * b) {
+    if (!a) return false;
+    const bool all_i32 = d->type == TTS_TYPE_I32 && a->type == TTS_TYPE_I32 && (!b || b->type == TTS_TYPE_I32);
+    return all_i32 || (is_fp(d) && is_fp(a) && (!b || is_fp(b)));
+}
 
 int tts_hip_supports_op(const tts_tensor * n) {
     if (!n) return 0;
@@ -816,25 +831,67 @@ int tts_hip_supports_op(const tts_tensor * n) {
         case TTS_OP_DUP: case TTS_OP_CONT: case TTS_OP_CPY:
             return (n->type == TTS_TYPE_F32 || n->type == TTS_TYPE_F16 || n->type == TTS_TYPE_I32) &&
                    (n->src[0]->type == TTS_TYPE_F32 || n->src[0]->type == TTS_TYPE_F16 || n->src[0]->type == TTS_TYPE_I32);
-        case TTS_OP_ADD: case TTS_OP_SUB: case TTS_OP_MUL: case TTS_OP_DIV:
-        case TTS_OP_SQR: case TTS_OP_SQRT: case TTS_OP_SIN: case TTS_OP_COS: case TTS_OP_SCALE: case TTS_OP_CLAMP:
-        case TTS_OP_LEAKY_RELU: case TTS_OP_ROUND: case TTS_OP_MOD: case TTS_OP_UNARY: case TTS_OP_CONCAT:
-        case TTS_OP_REPEAT: case TTS_OP_SUM_ROWS:
+        // The elementwise kernels read and write F32 / F16 through any strides (td_load / td_store); a quantized
+        // operand would be read as floats at block strides, and I32 would pass through float.
+        case TTS_OP_ADD: case TTS_OP_SUB: case TTS_OP_MUL: case TTS_OP_DIV: {
+            const tts_tensor * a = n->src[0];
+            const tts_tensor * b = n->src[1];
+            if (!is_fp(n) || !is_fp(a) || !is_fp(b)) return 0;
+            for (int i = 0; i < 4; ++i)  // ggml_can_repeat(src1, src0), dst of src0's shape
+                if (n->ne[i] != a->ne[i] || b->ne[i] < 1 || a->ne[i] % b->ne[i]) return 0;
             return 1;
+        }
+        case TTS_OP_SQR: case TTS_OP_SQRT: case TTS_OP_SIN: case TTS_OP_COS: case TTS_OP_SCALE: case TTS_OP_CLAMP:
+        case TTS_OP_LEAKY_RELU: case TTS_OP_ROUND: case TTS_OP_MOD: case TTS_OP_UNARY:
+            return is_fp(n) && is_fp(n->src[0]);
+        case TTS_OP_SUM_ROWS:
+            return is_fp(n) && is_fp(n->src[0]) && n->ne[0] == 1;
+        case TTS_OP_CONCAT:
+            return n->src[1] && movable(n, n->src[0], n->src[1]) && n->op_params[0] >= 0 && n->op_params[0] < 4;
+        case TTS_OP_REPEAT: {
+            if (!movable(n, n->src[0], nullptr)) return 0;
+            for (int i = 0; i < 4; ++i)
+                if (n->src[0]->ne[i] < 1 || n->ne[i] % n->src[0]->ne[i]) return 0;
+            return 1;
+        }
+        // The row kernels below index their source rows and write their destination through `float *`.
         case TTS_OP_NORM: case TTS_OP_RMS_NORM:
-            return is_f32(n->src[0]) && n->src[0]->nb[0] == 4;
-        case TTS_OP_SOFT_MAX:
-            return is_f32(n->src[0]);
-        case TTS_OP_ROPE:
-            return is_f32(n->src[0]);
+            return is_f32_rows(n->src[0]) && is_f32_rows(n);
+        case TTS_OP_SOFT_MAX: {
+            // k_soft_max takes row r at r * nb[1] on both sides (ggml asserts the same: contiguous src0 and dst),
+            // reads mask rows of ne00 elements at a stride of ne00, and has no ALiBi slope (max_bias)
+            const tts_tensor * m = n->src[1];
+            float max_bias;
+            memcpy(&max_bias, &n->op_params[1], 4);
+            if (max_bias != 0.0f || !is_f32(n->src[0]) || !is_f32(n) || !is_dense(n->src[0]) || !is_dense(n)) return 0;
+            if (m && (!is_fp(m) || m->nb[0] != tts_type_size(m->type))) return 0;
+            return 1;
+        }
+        case TTS_OP_ROPE: {
+            // k_rope: NORM (mode 0) and NEOX (mode 2) rotations, no YaRN ramp (ext_factor), positions a dense
+            // I32 vector over ne2, frequency factors a dense F32 vector over n_dims / 2
+            const tts_tensor * a = n->src[0];
+            const tts_tensor * pos = n->src[1];
+            const tts_tensor * ff = n->src[2];
+            float ext_factor;
+            memcpy(&ext_factor, &n->op_params[7], 4);
+            const int n_dims = n->op_params[1], mode = n->op_params[2];
+            if (!is_f32(a) || !is_f32_rows(n) || ext_factor != 0.0f || (mode & ~2)) return 0;
+            if (n_dims < 2 || (n_dims & 1) || n_dims > a->ne[0]) return 0;
+            if (!pos || pos->type != TTS_TYPE_I32 || pos->nb[0] != 4 ||
+                pos->ne[0] * pos->ne[1] * pos->ne[2] * pos->ne[3] < a->ne[2])
+                return 0;
+            if (ff && (!is_f32_rows(ff) || ff->ne[0] < n_dims / 2)) return 0;
+            return 1;
+        }
         case TTS_OP_IM2COL:
             return is_f32(n->src[1]) && n->op_params[6] == 0 && (n->type == TTS_TYPE_F16 || n->type == TTS_TYPE_F32);
         case TTS_OP_CONV_TRANSPOSE_1D:
             return is_f32(n->src[0]) && is_f32(n->src[1]) && n->op_params[4] >= 1;
         case TTS_OP_CUMSUM: case TTS_OP_UPSCALE: case TTS_OP_STFT: case TTS_OP_ISTFT: case TTS_OP_MAP_CUSTOM3: case TTS_OP_MAP_CUSTOM2:
             return tts::audio_op_supported(n);
-        case TTS_OP_GET_ROWS:
-            return n->src[1]->type == TTS_TYPE_I32 &&
+        case TTS_OP_GET_ROWS:  // k_get_rows reads dense table rows and writes rows of floats
+            return n->src[1]->type == TTS_TYPE_I32 && is_f32_rows(n) && n->src[0]->nb[0] == tts_type_size(n->src[0]->type) &&
                    (n->src[0]->type == TTS_TYPE_F32 || n->src[0]->type == TTS_TYPE_F16 || n->src[0]->type == TTS_TYPE_Q4_K ||
                     n->src[0]->type == TTS_TYPE_Q8_0 || n->src[0]->type == TTS_TYPE_Q5_0 || n->src[0]->type == TTS_TYPE_Q4_0 ||
                     (n->src[0]->type == TTS_TYPE_Q6_K && n->src[0]->ne[0] % 256 == 0));

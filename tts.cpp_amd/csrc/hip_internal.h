@@ -225,11 +225,16 @@ static __device__ __forceinline__ void unravel(int64_t k, const int64_t * ne, in
     i3 = k / ne[2];
 }
 
-static __device__ __forceinline__ float td_load(const TD & t, int64_t i0, int64_t i1, int64_t i2, int64_t i3) {
-    const char * p = t.data + i0 * t.nb[0] + i1 * t.nb[1] + i2 * t.nb[2] + i3 * t.nb[3];
+static __device__ __forceinline__ char * td_ptr(const TD & t, int64_t i0, int64_t i1, int64_t i2, int64_t i3) {
+    return t.data + i0 * t.nb[0] + i1 * t.nb[1] + i2 * t.nb[2] + i3 * t.nb[3];
+}
+static __device__ __forceinline__ float td_load_at(const TD & t, const char * p) {
     if (t.type == TTS_TYPE_F16) return __half2float(*(const __half *)p);
     if (t.type == TTS_TYPE_I32) return (float)*(const int32_t *)p;
     return *(const float *)p;
+}
+static __device__ __forceinline__ float td_load(const TD & t, int64_t i0, int64_t i1, int64_t i2, int64_t i3) {
+    return td_load_at(t, td_ptr(t, i0, i1, i2, i3));
 }
 static __device__ __forceinline__ void td_store(const TD & t, int64_t i0, int64_t i1, int64_t i2, int64_t i3, float v) {
     char * p = t.data + i0 * t.nb[0] + i1 * t.nb[1] + i2 * t.nb[2] + i3 * t.nb[3];

@@ -14,8 +14,7 @@ __global__ void k_cpy(TD dst, TD src, int64_t n) {
         unravel(k, src.ne, a0, a1, a2, a3);
         unravel(k, dst.ne, b0, b1, b2, b3);
         if (src.type == TTS_TYPE_I32 && dst.type == TTS_TYPE_I32) {
-            *(int32_t *)(dst.data + b0 * dst.nb[0] + b1 * dst.nb[1] + b2 * dst.nb[2] + b3 * dst.nb[3]) =
-                *(const int32_t *)(src.data + a0 * src.nb[0] + a1 * src.nb[1] + a2 * src.nb[2] + a3 * src.nb[3]);
+            *(int32_t *)td_ptr(dst, b0, b1, b2, b3) = *(const int32_t *)td_ptr(src, a0, a1, a2, a3);
         } else {
             td_store(dst, b0, b1, b2, b3, td_load(src, a0, a1, a2, a3));
         }
@@ -450,25 +449,31 @@ void launch_embed_sum(tts_hip_backend * be, const tts_tensor * out, const tts_te
 
 // ---- CONCAT / REPEAT / SUM_ROWS ----
 __global__ void k_concat(TD dst, TD a, TD b, int dim, int64_t n) {
+    const bool i32 = dst.type == TTS_TYPE_I32 && a.type == TTS_TYPE_I32 && b.type == TTS_TYPE_I32;
     for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
         int64_t i[4];
         unravel(k, dst.ne, i[0], i[1], i[2], i[3]);
-        float v;
-        if (i[0] < a.ne[0] && i[1] < a.ne[1] && i[2] < a.ne[2] && i[3] < a.ne[3]) v = td_load(a, i[0], i[1], i[2], i[3]);
+        const bool first = i[0] < a.ne[0] && i[1] < a.ne[1] && i[2] < a.ne[2] && i[3] < a.ne[3];
+        const char * sp;
+        if (first) sp = td_ptr(a, i[0], i[1], i[2], i[3]);
         else {
             i[dim] -= a.ne[dim];
-            v = td_load(b, i[0], i[1], i[2], i[3]);
+            sp = td_ptr(b, i[0], i[1], i[2], i[3]);
             i[dim] += a.ne[dim];
         }
-        td_store(dst, i[0], i[1], i[2], i[3], v);
+        if (i32) *(int32_t *)td_ptr(dst, i[0], i[1], i[2], i[3]) = *(const int32_t *)sp;  // ids and positions: no trip through float
+        else td_store(dst, i[0], i[1], i[2], i[3], first ? td_load_at(a, sp) : td_load_at(b, sp));
     }
 }
 
 __global__ void k_repeat(TD dst, TD a, int64_t n) {
+    const bool i32 = dst.type == TTS_TYPE_I32 && a.type == TTS_TYPE_I32;
     for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
         int64_t i0, i1, i2, i3;
         unravel(k, dst.ne, i0, i1, i2, i3);
-        td_store(dst, i0, i1, i2, i3, td_load(a, i0 % a.ne[0], i1 % a.ne[1], i2 % a.ne[2], i3 % a.ne[3]));
+        const char * sp = td_ptr(a, i0 % a.ne[0], i1 % a.ne[1], i2 % a.ne[2], i3 % a.ne[3]);
+        if (i32) *(int32_t *)td_ptr(dst, i0, i1, i2, i3) = *(const int32_t *)sp;
+        else td_store(dst, i0, i1, i2, i3, td_load_at(a, sp));
     }
 }
 

@@ -283,7 +283,7 @@ enum tts_hip_option {
                                      ONE 1024-thread launch per attention (k_attn_fused; default 0 = off: the split pair,
                                      TTS_HIP_OPT_ATTN_SPLIT; tests and studies use 128) */
     TTS_HIP_OPT_GEMM_Q8 = 18,     /* 1 (default) = Q8_0 products of more than 8 columns run the int8 matrix-core GEMM
-                                     (k_gemm_q8_0, bit-identical); 0 = one GEMV launch per 8 columns */
+                                     (k_gemm_b32 / k_gemm_b32s over BlkQ8_0, bit-identical); 0 = one GEMV launch per 8 columns */
     TTS_HIP_OPT_BGEMM_F32 = 19,   /* 1 (default) = batched float products (attention over many queries: encoders,
                                      prefill) run the tiled f64-accumulating GEMM; 0 = the one-wave-per-output kernel */
     TTS_HIP_OPT_CU_PARTITION = 20, /* (index << 8) | count, count > 1: the backend's stream runs on partition `index` of
@@ -311,9 +311,9 @@ enum tts_hip_option {
     TTS_HIP_OPT_GEMV_Q80_PRO = 27, /* 1 (default): Q8_0 GEMVs of <= 8 columns with K % 256 == 0 quantize (and, fused with a
                                      preceding LayerNorm / RMSNorm of K <= 4096, normalize) the activation in every
                                      workgroup: one launch instead of norm + quantize + GEMV; 0 = separate launches */
-    TTS_HIP_OPT_GEMV_Q80_SLAB = 28, /* 1 (default): Q8_0 GEMVs with K % 256 == 0 run the slab kernel (a workgroup's rows
+    TTS_HIP_OPT_GEMV_Q80_SLAB = 28, /* 1 (default): Q8_0 GEMVs with K % 256 == 0 run the slab kernel (k_gemv_b32s: a workgroup's rows
                                      fetched whole by LDS-DMA, terms then ggml's block-order chain from LDS);
-                                     0 = the (row, block)-per-thread kernel */
+                                     0 = the (row, block)-per-thread kernel (k_gemv_b32) */
     TTS_HIP_OPT_GEMV_Q80_RW = 29,  /* slab Q8_0 GEMV rows per workgroup (0 = auto: the most that still fills every CU) */
     TTS_HIP_OPT_GEMM_Q8_STAGED = 30, /* many-column Q8_0 GEMM with K % 256 == 0: 2 (default) = staged LDS-DMA kernel over
                                      64 x 128 output tiles, 1 = over 64 x 64 tiles, 0 = the direct-load kernel */
@@ -359,19 +359,19 @@ enum tts_hip_option {
                                      3 = the early residual alone; 4 = the fold alone; 0 = the relay and the residual read
                                      at the store */
     TTS_HIP_OPT_GEMV_Q50_SLAB = 45, /* 1 (default): Q5_0 GEMVs with K % 256 == 0 (rows of 176 K / 256 bytes) run the slab kernel
-                                      (k_gemv_q5_0s, as TTS_HIP_OPT_GEMV_Q80_SLAB); 0 = the (row, block)-per-thread kernel.
+                                      (k_gemv_b32s over BlkQ5_0, as TTS_HIP_OPT_GEMV_Q80_SLAB); 0 = the (row, block)-per-thread kernel.
                                       TTS_HIP_OPT_GEMV_Q80_PRO governs the prologue of both types (the activation is Q8_0) */
     TTS_HIP_OPT_GEMV_Q50_RW = 46,  /* slab Q5_0 GEMV rows per workgroup (0 = auto: the most that still fills every CU) */
     TTS_HIP_OPT_GEMM_Q5 = 47,      /* 1 (default) = Q5_0 products of more than 8 columns run the int8 matrix-core GEMM
-                                      (k_gemm_q5_0 / k_gemm_q5_0s, bit-identical); 0 = one GEMV launch per 8 columns */
+                                      (k_gemm_b32 / k_gemm_b32s over BlkQ5_0, bit-identical); 0 = one GEMV launch per 8 columns */
     TTS_HIP_OPT_GEMM_Q5_STAGED = 48, /* many-column Q5_0 GEMM with K % 256 == 0: 2 (default) = staged kernel over 64 x 128
                                       output tiles, 1 = over 64 x 64 tiles, 0 = the direct-load kernel */
     TTS_HIP_OPT_GEMV_Q40_SLAB = 49, /* 1 (default): Q4_0 GEMVs with K % 256 == 0 (rows of 144 K / 256 bytes) run the slab kernel
-                                      (k_gemv_q4_0s, as TTS_HIP_OPT_GEMV_Q80_SLAB); 0 = the (row, block)-per-thread kernel.
+                                      (k_gemv_b32s over BlkQ4_0, as TTS_HIP_OPT_GEMV_Q80_SLAB); 0 = the (row, block)-per-thread kernel.
                                       TTS_HIP_OPT_GEMV_Q80_PRO governs the prologue of all three types (the activation is Q8_0) */
     TTS_HIP_OPT_GEMV_Q40_RW = 50,  /* slab Q4_0 GEMV rows per workgroup (0 = auto: the most that still fills every CU) */
     TTS_HIP_OPT_GEMM_Q4_0 = 51,    /* 1 (default) = Q4_0 products of more than 8 columns run the int8 matrix-core GEMM
-                                      (k_gemm_q4_0 / k_gemm_q4_0s, bit-identical); 0 = one GEMV launch per 8 columns */
+                                      (k_gemm_b32 / k_gemm_b32s over BlkQ4_0, bit-identical); 0 = one GEMV launch per 8 columns */
     TTS_HIP_OPT_GEMM_Q4_0_STAGED = 52, /* many-column Q4_0 GEMM with K % 256 == 0: 2 (default) = staged kernel over 64 x 128
                                       output tiles, 1 = over 64 x 64 tiles, 0 = the direct-load kernel */
     TTS_HIP_OPT_CONV_VFMA = 53,   /* fused conv_1d on f64 vector FMAs (k_conv1d_f64v: lane = output position, one output channel

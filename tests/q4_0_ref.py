@@ -134,10 +134,10 @@ def twin_gguf(src, dst):
 # ---- the kernel cases of tests/test_q4_0_gpu.py, shared with the CPU check that R1 tells the two orders apart on them ----
 # K % 256 != 0 -> the general kernel only; N = 1, N % RW != 0; (4096, 1024) fills every CU with 4-row slabs
 GEMV_SHAPES = [(96, 5), (160, 33), (256, 1), (256, 3), (1024, 33), (2048, 64), (4096, 1024)]
-GEMV_COLS = [1, 2, 5, 8]
+GEMV_COLS = [1, 2, 3, 5, 8]
 # (96, 70): K % 256 != 0 and rows / columns that fill no 64 x 64 tile; N = 1000: a ragged last row tile
 GEMM_SHAPES = [(256, 16), (1024, 1000), (4096, 1024), (96, 70)]
-GEMM_COLS = [9, 17, 32, 100]
+GEMM_COLS = [9, 17, 32, 100, 130]
 
 
 def _case(seed, K, N, M):

@@ -206,7 +206,9 @@ def run_parler_case(wtype, shape, n, ifaces=None):
 
 Q4_K, Q8_0, Q5_0, F16, F32 = ttship.Q4_K, ttship.Q8_0, ttship.Q5_0, ttship.F16, ttship.F32
 
-# (weights, shape, members): the id names the kernel the coalesced q / k / v group is meant to run on
+# (weights, shape, members): the id names the kernel the coalesced q / k / v group is meant to run on.  The Q8_0 / Q5_0
+# ids are kept stable from when each format had kernels of its own: q8_0s / q5_0s is k_gemv_b32s, q8_0 / q5_0
+# k_gemv_b32 and the gemm ids k_gemm_b32, over BlkQ8_0 / BlkQ5_0
 CASES = [
     # lane layout, K >= 8 * QK_K: the q / k / v group split into single-matrix unique-load launches
     pytest.param(Q4_K, H2048, 3, id="q4k-h2048-n3-k_gemv_q4_K_u-split"),

@@ -217,14 +217,15 @@ Q80_PATHS = {"slab_pro": (1, 1, 0), "slab": (1, 0, 0), "rows_pro": (0, 1, 0), "r
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("path", list(Q80_PATHS))
-@pytest.mark.parametrize("K,N", [(2048, 2048), (2048, 512), (8192, 64), (1024, 1024), (64, 7), (768, 33), (4096, 1000)])
+@pytest.mark.parametrize("K,N", [(2048, 2048), (2048, 512), (8192, 64), (1024, 1024), (64, 7), (768, 33), (4096, 1000), (96, 5)])
 @pytest.mark.parametrize("M", [1, 2, 3, 8, 9, 64, 300])
 def test_q8_0(hip, path, K, N, M):
-    """M > 8: the int8 matrix-core GEMM (k_gemm_q8_0): per-block exact int dots, ggml's f32 chain.
+    """M > 8: the int8 matrix-core GEMM (k_gemm_b32<BlkQ8_0>): per-block exact int dots, ggml's f32 chain.
     M <= 8, K % 256 == 0: the slab kernel (TTS_HIP_OPT_GEMV_Q80_SLAB = 1; rows per workgroup auto, 1 or
     32, partial last workgroups) or the (row, block)-per-thread kernel, each with the activation quantized
     to Q8_0 inside every workgroup (TTS_HIP_OPT_GEMV_Q80_PRO = 1: quantize_row_q8_0 per 32 elements) or by
-    the separate quantize launch."""
+    the separate quantize launch.  (96, 5): three blocks per row make rows of 102 B, so every other row is only
+    2-B aligned (the (row, block)-per-thread kernel, k_gemv_b32<BlkQ8_0>)."""
     slab, pro, rw = Q80_PATHS[path]
     if M > 8 and path != "slab_pro":
         pytest.skip("M > 8 runs the matrix-core GEMM on every path")

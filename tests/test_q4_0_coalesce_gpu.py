@@ -81,7 +81,8 @@ def reference(shape, r):
 
 
 # H256: the slab kernel with the LN / quantize prologue (12 members: 8 + 4 column chunks over it); H320 (K % 256 != 0):
-# the general kernel k_gemv_q4_0 at 3 members, and at 12 the K / V store runs on the matrix-core GEMM k_gemm_q4_0
+# the general kernel k_gemv_b32<BlkQ4_0> at 3 members, and at 12 the K / V store runs on the matrix-core GEMM
+# k_gemm_b32<BlkQ4_0>.  The ids are kept stable from when Q4_0 had kernels of its own (q4_0s: k_gemv_b32s)
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape,n", [pytest.param(cp.H256, 3, id="h256-n3-k_gemv_q4_0s"), pytest.param(cp.H256, 12, id="h256-n12-k_gemv_q4_0s-chunks"),
                                      pytest.param(cp.H320, 3, id="h320-n3-k_gemv_q4_0"), pytest.param(cp.H320, 12, id="h320-n12-k_gemm_q4_0")])

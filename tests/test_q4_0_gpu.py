@@ -137,7 +137,7 @@ def test_graph_layer_norm_into_mul_mat(hip, mask, M):
     """General d: the oracle computes the LayerNorm chain, R1 the product of its output.  Random weights on a
     normalized activation: |sumi| stays below 2^13, where both association orders give the same bits, so this case
     does not see the order.  It checks the prologue's LayerNorm and quantization and the route's plumbing; the
-    order is pinned by test_gemv and test_gemm, whose term code (q40_term) these instantiations share."""
+    order is pinned by test_gemv and test_gemm, whose term code (BlkQ4_0::term) these instantiations share."""
     K, N = 512, 96
     w = q4.rand_q4_0(np.random.default_rng(M), N, K)
     x, gam, bet = rnd(1, M, K) + 0.25, rnd(2, K) * 0.1 + 1.0, rnd(3, K) * 0.02

@@ -65,7 +65,7 @@ def test_ragged_rows_are_refused(hip):
 
 # K % 256 != 0 -> the general kernel only; N = 1, N % RW != 0; (4096, 1024) fills every CU with 4-row slabs
 @pytest.mark.parametrize("K,N", [(96, 5), (160, 33), (256, 1), (256, 3), (1024, 33), (2048, 64), (4096, 1024)])
-@pytest.mark.parametrize("M", [1, 2, 5, 8])
+@pytest.mark.parametrize("M", [1, 2, 3, 5, 8])
 def test_gemv(hip, K, N, M):
     rng = np.random.default_rng(K * 7 + N + M)
     w = q5.rand_q5_0(rng, N, K)
@@ -96,7 +96,7 @@ def test_gemv_slab_rows_per_workgroup(hip, rw):
 
 # (96, 70): K % 256 != 0 and rows / columns that fill no 64 x 64 tile; N = 1000: a ragged last row tile
 @pytest.mark.parametrize("K,N", [(256, 16), (1024, 1000), (4096, 1024), (96, 70)])
-@pytest.mark.parametrize("M", [9, 17, 32, 100])
+@pytest.mark.parametrize("M", [9, 17, 32, 100, 130])
 def test_gemm(hip, K, N, M):
     rng = np.random.default_rng(K * 13 + N + M)
     w = q5.rand_q5_0(rng, N, K)

@@ -941,38 +941,32 @@ extern "C" int tts_hip_set_option(tts_hip_backend_t be, int option, int value) {
         case TTS_HIP_OPT_GEMV_KRELAY: be->gemv_kr = value != 0; return 0;
         case TTS_HIP_OPT_GEMV_KRELAY_LOOP: be->gemv_kr_loop = value != 0; return 0;
         case TTS_HIP_OPT_GEMV_Q80_PRO: be->gemv_q80_pro = value != 0; return 0;
-        case TTS_HIP_OPT_GEMV_Q80_SLAB: be->gemv_q80_slab = value != 0; return 0;
         case TTS_HIP_OPT_GEMV_KR_INKERNEL:
             if (value < 0) return TTS_STATUS_BAD_ARG;
             be->gemv_kr_ink = value;
             return 0;
-        case TTS_HIP_OPT_GEMM_Q8_STAGED:
-            if (value < 0 || value > 2) return TTS_STATUS_BAD_ARG;
-            be->gemm_q8_staged = value;
+        // the Q8_0 / Q5_0 / Q4_0 kernels: one option record per format
+        case TTS_HIP_OPT_GEMV_Q80_SLAB:
+        case TTS_HIP_OPT_GEMV_Q50_SLAB:
+        case TTS_HIP_OPT_GEMV_Q40_SLAB:
+            be->b32[option == TTS_HIP_OPT_GEMV_Q80_SLAB ? 0 : option == TTS_HIP_OPT_GEMV_Q50_SLAB ? 1 : 2].slab = value != 0;
             return 0;
         case TTS_HIP_OPT_GEMV_Q80_RW:
-            if (value < 0 || value > 32 || (value & (value - 1))) return TTS_STATUS_BAD_ARG;
-            be->gemv_q80_rw = value;
-            return 0;
-        case TTS_HIP_OPT_GEMV_Q50_SLAB: be->gemv_q50_slab = value != 0; return 0;
         case TTS_HIP_OPT_GEMV_Q50_RW:
-            if (value < 0 || value > 32 || (value & (value - 1))) return TTS_STATUS_BAD_ARG;
-            be->gemv_q50_rw = value;
-            return 0;
-        case TTS_HIP_OPT_GEMM_Q5: be->gemm_q5 = value != 0; return 0;
-        case TTS_HIP_OPT_GEMM_Q5_STAGED:
-            if (value < 0 || value > 2) return TTS_STATUS_BAD_ARG;
-            be->gemm_q5_staged = value;
-            return 0;
-        case TTS_HIP_OPT_GEMV_Q40_SLAB: be->gemv_q40_slab = value != 0; return 0;
         case TTS_HIP_OPT_GEMV_Q40_RW:
             if (value < 0 || value > 32 || (value & (value - 1))) return TTS_STATUS_BAD_ARG;
-            be->gemv_q40_rw = value;
+            be->b32[option == TTS_HIP_OPT_GEMV_Q80_RW ? 0 : option == TTS_HIP_OPT_GEMV_Q50_RW ? 1 : 2].rw = value;
             return 0;
-        case TTS_HIP_OPT_GEMM_Q4_0: be->gemm_q4_0 = value != 0; return 0;
+        case TTS_HIP_OPT_GEMM_Q8:
+        case TTS_HIP_OPT_GEMM_Q5:
+        case TTS_HIP_OPT_GEMM_Q4_0:
+            be->b32[option == TTS_HIP_OPT_GEMM_Q8 ? 0 : option == TTS_HIP_OPT_GEMM_Q5 ? 1 : 2].gemm = value != 0;
+            return 0;
+        case TTS_HIP_OPT_GEMM_Q8_STAGED:
+        case TTS_HIP_OPT_GEMM_Q5_STAGED:
         case TTS_HIP_OPT_GEMM_Q4_0_STAGED:
             if (value < 0 || value > 2) return TTS_STATUS_BAD_ARG;
-            be->gemm_q4_0_staged = value;
+            be->b32[option == TTS_HIP_OPT_GEMM_Q8_STAGED ? 0 : option == TTS_HIP_OPT_GEMM_Q5_STAGED ? 1 : 2].staged = value;
             return 0;
         case TTS_HIP_OPT_ATTN_KS: be->attn_ks = value; return 0;
         case TTS_HIP_OPT_GEMV_NW_MIN: be->gemv_nw_min = value; return 0;
@@ -989,7 +983,6 @@ extern "C" int tts_hip_set_option(tts_hip_backend_t be, int option, int value) {
             be->gemv_kr_tail = value;
             return 0;
         case TTS_HIP_OPT_GEMM_KR_NW: be->gemm_kr_nw = value == 8 ? 8 : 4; return 0;
-        case TTS_HIP_OPT_GEMM_Q8: be->gemm_q8 = value != 0; return 0;
         case TTS_HIP_OPT_CU_PARTITION: {
             const int count = value & 0xFF, index = (value >> 8) & 0xFF;
             const bool inter = (value >> 16) & 1;

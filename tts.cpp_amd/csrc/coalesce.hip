@@ -214,7 +214,6 @@ void copy_options(tts_hip_backend * d, const tts_hip_backend * s) {
     d->attn_pv_uv16 = s->attn_pv_uv16;
     d->attn_fused_minp = s->attn_fused_minp;
     d->gemv_unique = s->gemv_unique;
-    d->gemm_q8 = s->gemm_q8;
     d->bgemm_f32 = s->bgemm_f32;
     d->gemv_f32_wide = s->gemv_f32_wide;
     d->gemm_kr_nw = s->gemm_kr_nw;
@@ -224,17 +223,7 @@ void copy_options(tts_hip_backend * d, const tts_hip_backend * s) {
     d->gemv_kr_loop = s->gemv_kr_loop;
     d->gemv_kr_tail = s->gemv_kr_tail;
     d->gemv_q80_pro = s->gemv_q80_pro;
-    d->gemv_q80_slab = s->gemv_q80_slab;
-    d->gemv_q80_rw = s->gemv_q80_rw;
-    d->gemm_q8_staged = s->gemm_q8_staged;
-    d->gemv_q50_slab = s->gemv_q50_slab;
-    d->gemv_q50_rw = s->gemv_q50_rw;
-    d->gemm_q5 = s->gemm_q5;
-    d->gemm_q5_staged = s->gemm_q5_staged;
-    d->gemv_q40_slab = s->gemv_q40_slab;
-    d->gemv_q40_rw = s->gemv_q40_rw;
-    d->gemm_q4_0 = s->gemm_q4_0;
-    d->gemm_q4_0_staged = s->gemm_q4_0_staged;
+    d->b32 = s->b32;
     d->gemv_kr_ink = s->gemv_kr_ink;
     d->gemm_kr_ct2 = s->gemm_kr_ct2;
     d->gemm_kr_xcd = s->gemm_kr_xcd;

@@ -72,6 +72,8 @@ TTS_HD bool wtype_q8k_act(int t) { return t == TTS_TYPE_Q4_K || t == TTS_TYPE_Q6
 // the activation type a weight type's products quantize src1 to (ggml's vec_dot_type): Q4_0, Q5_0 and Q8_0
 // all take Q8_0
 TTS_HD bool wtype_q80_act(int t) { return t == TTS_TYPE_Q8_0 || t == TTS_TYPE_Q5_0 || t == TTS_TYPE_Q4_0; }
+// those three in a fixed order: the index of a format's option record (tts_hip_backend::b32)
+TTS_HD int b32_index(int t) { return t == TTS_TYPE_Q8_0 ? 0 : t == TTS_TYPE_Q5_0 ? 1 : 2; }
 
 // Host fp16 conversion: same bit-exact algorithm as ggml_compute_fp{16,32}_to_fp{32,16}.
 inline float fp16_to_fp32_host(uint16_t h) {

@@ -2320,7 +2320,7 @@ static int run_gemv_item(tts_hip_backend * be, const Item & it, const Item * xat
         j.res = (const float *)it.res->data;
         j.rcs = (int64_t)(it.res->nb[1] / 4);
     }
-    // Q8_0 / Q5_0 with <= 8 columns (K % 256 == 0): the same prologue, writing Q8_0 blocks (k_gemv_q8_0 / q5_0<MC, PRO>)
+    // Q8_0 / Q5_0 / Q4_0 with <= 8 columns (K % 256 == 0): the same prologue, writing Q8_0 blocks (k_gemv_b32 / k_gemv_b32s<F, MC, PRO>)
     const bool q80pro = wtype_q80_act(j.wtype) && j.K % QK_K == 0 && j.M <= 8 && (it.ln || be->gemv_q80_pro);
     if (wtype_q8k_act(j.wtype) || q80pro) {
         // the kernel quantizes (and normalizes) src1 itself in every workgroup

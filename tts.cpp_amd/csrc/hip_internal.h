@@ -6,6 +6,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <array>
 #include <atomic>
 #include <deque>
 #include <mutex>
@@ -160,34 +161,12 @@ __device__ __forceinline__ int8_t q80_quant_elem(float v, float & d_out) {
 __device__ __forceinline__ uint32_t q50_himask(uint32_t nqh, int s) {  // nqh = ~qh; weights s .. s + 3
     return ((((nqh >> s) & 0xFu) * 0x00204081u) & 0x01010101u) * 0xF0u;
 }
-// the block's 32 int8 weights: wv[i] = weights 4 i .. 4 i + 3 (i < 4: low nibbles, i >= 4: high nibbles)
-__device__ __forceinline__ void q50_unpack(uint32_t qh, const uint32_t (&qs)[4], int (&wv)[8]) {
-    const uint32_t nqh = ~qh;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        wv[i] = (int)((qs[i] & 0x0F0F0F0Fu) | q50_himask(nqh, 4 * i));
-        wv[4 + i] = (int)(((qs[i] >> 4) & 0x0F0F0F0Fu) | q50_himask(nqh, 16 + 4 * i));
-    }
-}
 // Q4_0: four weights per dword: a byte's nibble n in 0 .. 15 becomes the int8 n - 8 in four operations on the
 // dword (five for the high nibbles' shift): t = n ^ 8 is n - 8 for n >= 8 and n + 8 (bit 3 set) for n < 8, where
 // n - 8 is t with 0xF0 on top; (t & 0x08) * 0x1E = 0xF0 stays inside its byte.
 __device__ __forceinline__ uint32_t q40_s8(uint32_t nib) {  // nib: four bytes 0 .. 15
     const uint32_t t = nib ^ 0x08080808u;
     return t | ((t & 0x08080808u) * 0x1Eu);
-}
-// the block's 32 int8 weights q - 8: wv[i] = weights 4 i .. 4 i + 3 (i < 4: low nibbles, i >= 4: high nibbles)
-__device__ __forceinline__ void q40_unpack(const uint32_t (&qs)[4], int (&wv)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        wv[i] = (int)q40_s8(qs[i] & 0x0F0F0F0Fu);
-        wv[4 + i] = (int)q40_s8((qs[i] >> 4) & 0x0F0F0F0Fu);
-    }
-}
-// ggml_vec_dot_q4_0_q8_0's term: ((float)sumi * d_w) * d_x, each product rounded -- not the Q8_0 / Q5_0 kernels'
-// sumi * (d_w * d_x), which differs in the last bit for about one term in ten
-__device__ __forceinline__ float q40_term(int sumi, float dw, float dx) {
-    return __fmul_rn(__fmul_rn((float)sumi, dw), dx);
 }
 // exact int32 dot of a block's 32 int8 weights with 32 int8 activations (x0 = elements 0 .. 15, x1 = 16 .. 31)
 __device__ __forceinline__ int q50_dot(const int (&wv)[8], const int4 x0, const int4 x1) {
@@ -200,6 +179,124 @@ __device__ __forceinline__ int q50_dot(const int (&wv)[8], const int4 x0, const 
     s = __builtin_amdgcn_sdot4(wv[6], x1.z, s, false);
     s = __builtin_amdgcn_sdot4(wv[7], x1.w, s, false);
     return s;
+}
+// The three 32-weight formats whose activation is Q8_0, as traits of the shared kernel bodies (k_gemv_b32,
+// k_gemv_b32s, k_gemm_b32, k_gemm_b32s in k_gemv.hip; k_lstm_step_q in k_fused.hip).  A block is {f16 d;
+// payload}, BYTES in all at a 2-B aligned address, the payload ND = (BYTES - 2) / 4 dwords.  Each trait gives
+//   unpack(q, wv)   the payload dwords -> the block's 32 int8 weights, wv[i] = weights 4 i .. 4 i + 3
+//   QOFF, sel(kq), nsh(kq), octet(q0, q1, blk, kq, nsh)
+//                   the MFMA A operand of lane group kq, weights 8 kq .. 8 kq + 7 paired with the activation's same
+//                   octet: q0, q1 are the eight payload bytes at blk + QOFF + 8 * sel(kq) (b32_octet / b32_octet_lds
+//                   fetch them); nsh(kq), the nibble shift of the two nibble formats, is taken once at a kernel's top
+//   term(sumi, dw, dx)
+//                   the block's f32 term with ggml_vec_dot_<format>_q8_0's association and roundings
+struct BlkQ8_0 {  // {d; int8 qs[32]}
+    static constexpr int TYPE = TTS_TYPE_Q8_0, BYTES = 34, ND = 8;
+    static __device__ __forceinline__ void unpack(const uint32_t (&q)[ND], int (&wv)[8]) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) wv[i] = (int)q[i];
+    }
+    static constexpr int QOFF = 2;
+    static __device__ __forceinline__ int sel(int kq) { return kq; }
+    static __device__ __forceinline__ int nsh(int) { return 0; }
+    static __device__ __forceinline__ long octet(uint32_t q0, uint32_t q1, const uint8_t *, int, int) {
+        return (long)(((uint64_t)q1 << 32) | q0);
+    }
+    static __device__ __forceinline__ float term(int sumi, float dw, float dx) {
+        return __fmul_rn((float)sumi, __fmul_rn(dw, dx));
+    }
+};
+struct BlkQ5_0 {  // {d; u8 qh[4]; u8 qs[16]}: q[0] = qh, q[1 .. 4] = qs; weights q - 16 in [-16, 15]
+    static constexpr int TYPE = TTS_TYPE_Q5_0, BYTES = 22, ND = 5;
+    // i < 4: low nibbles, i >= 4: high nibbles
+    static __device__ __forceinline__ void unpack(const uint32_t (&q)[ND], int (&wv)[8]) {
+        const uint32_t nqh = ~q[0];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            wv[i] = (int)((q[1 + i] & 0x0F0F0F0Fu) | q50_himask(nqh, 4 * i));
+            wv[4 + i] = (int)(((q[1 + i] >> 4) & 0x0F0F0F0Fu) | q50_himask(nqh, 16 + 4 * i));
+        }
+    }
+    // groups 0, 1 the low nibbles of qs[0..7] / qs[8..15], groups 2, 3 their high nibbles, each with byte kq of qh
+    static constexpr int QOFF = 6;
+    static __device__ __forceinline__ int sel(int kq) { return kq & 1; }
+    static __device__ __forceinline__ int nsh(int kq) { return (kq >> 1) * 4; }  // high nibbles for weights 16 .. 31
+    static __device__ __forceinline__ long octet(uint32_t q0, uint32_t q1, const uint8_t * blk, int kq, int nsh) {
+        const uint32_t nqh = ~(uint32_t)blk[2 + kq];
+        const uint32_t lo = ((q0 >> nsh) & 0x0F0F0F0Fu) | q50_himask(nqh, 0);
+        const uint32_t hi = ((q1 >> nsh) & 0x0F0F0F0Fu) | q50_himask(nqh, 4);
+        return (long)(((uint64_t)hi << 32) | lo);
+    }
+    static __device__ __forceinline__ float term(int sumi, float dw, float dx) {
+        return __fmul_rn((float)sumi, __fmul_rn(dw, dx));
+    }
+};
+struct BlkQ4_0 {  // {d; u8 qs[16]}: q[0 .. 3] = qs; weights q - 8 in [-8, 7]
+    static constexpr int TYPE = TTS_TYPE_Q4_0, BYTES = 18, ND = 4;
+    // i < 4: low nibbles, i >= 4: high nibbles
+    static __device__ __forceinline__ void unpack(const uint32_t (&q)[ND], int (&wv)[8]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            wv[i] = (int)q40_s8(q[i] & 0x0F0F0F0Fu);
+            wv[4 + i] = (int)q40_s8((q[i] >> 4) & 0x0F0F0F0Fu);
+        }
+    }
+    // groups 0, 1 the low nibbles of qs[0..7] / qs[8..15], groups 2, 3 their high nibbles, each made q - 8 by q40_s8
+    static constexpr int QOFF = 2;
+    static __device__ __forceinline__ int sel(int kq) { return kq & 1; }
+    static __device__ __forceinline__ int nsh(int kq) { return (kq >> 1) * 4; }  // high nibbles for weights 16 .. 31
+    static __device__ __forceinline__ long octet(uint32_t q0, uint32_t q1, const uint8_t *, int, int nsh) {
+        const uint32_t lo = q40_s8((q0 >> nsh) & 0x0F0F0F0Fu);
+        const uint32_t hi = q40_s8((q1 >> nsh) & 0x0F0F0F0Fu);
+        return (long)(((uint64_t)hi << 32) | lo);
+    }
+    // ((float)sumi * d_w) * d_x, each product rounded -- not the other two formats' sumi * (d_w * d_x), which
+    // differs in the last bit for about one term in ten
+    static __device__ __forceinline__ float term(int sumi, float dw, float dx) {
+        return __fmul_rn(__fmul_rn((float)sumi, dw), dx);
+    }
+};
+// The forms in which the kernel bodies meet a block, the same for every format F.
+// A block at any 2-B aligned address `bp` (P: a pointer to its 16-bit words, global or generic): BYTES / 2 16-bit
+// loads -> the fp16 d and the payload dwords (then F::unpack)
+template <class F, class P>
+__device__ __forceinline__ void b32_load(P bp, uint16_t & d, uint32_t (&q)[F::ND]) {
+    d = bp[0];
+#pragma unroll
+    for (int k = 0; k < F::ND; ++k) q[k] = (uint32_t)bp[1 + 2 * k] | ((uint32_t)bp[2 + 2 * k] << 16);
+}
+// The block pair (2k, 2k + 1) as its BYTES / 2 dwords from a 4-B aligned address: d0 | payload 0 (the funnel-shifted
+// dwords) | d1, payload 1 (whole dwords)
+template <class F>
+__device__ __forceinline__ void b32_pair(const uint32_t (&w)[F::BYTES / 2], float & d0, float & d1, int (&q0)[8], int (&q1)[8]) {
+    d0 = dev_fp16_to_fp32((uint16_t)(w[0] & 0xFFFFu));
+    d1 = dev_fp16_to_fp32((uint16_t)(w[F::ND] >> 16));
+    uint32_t p0[F::ND], p1[F::ND];
+#pragma unroll
+    for (int i = 0; i < F::ND; ++i) {
+        p0[i] = __builtin_amdgcn_alignbit(w[i + 1], w[i], 16);
+        p1[i] = w[F::ND + 1 + i];
+    }
+    F::unpack(p0, q0);
+    F::unpack(p1, q1);
+}
+// Lane group kq's MFMA A operand from a 2-B aligned block in global memory: its eight payload bytes as four 16-bit loads
+template <class F>
+__device__ __forceinline__ long b32_octet(const uint8_t * blk, int kq, int nsh) {
+    const uint16_t * q = (const uint16_t *)(blk + F::QOFF + 8 * F::sel(kq));
+    const uint32_t q0 = (uint32_t)q[0] | ((uint32_t)q[1] << 16), q1 = (uint32_t)q[2] | ((uint32_t)q[3] << 16);
+    return F::octet(q0, q1, blk, kq, nsh);
+}
+// The same from a staged LDS image (`base` 4-B aligned, the block `boff` bytes into it): the eight bytes start 0 or
+// 2 B off a dword, so three dwords and two funnel shifts
+template <class F>
+__device__ __forceinline__ long b32_octet_lds(const char * base, int boff, int kq, int nsh) {
+    const int off = boff + F::QOFF + 8 * F::sel(kq);
+    const uint32_t * p = (const uint32_t *)(base + (off & ~3));
+    const uint32_t d0 = p[0], d1 = p[1], d2 = p[2];
+    const uint32_t sh = (off & 3) * 8;
+    const uint32_t q0 = __builtin_amdgcn_alignbit(d1, d0, sh), q1 = __builtin_amdgcn_alignbit(d2, d1, sh);
+    return F::octet(q0, q1, (const uint8_t *)(base + boff), kq, nsh);
 }
 #endif
 
@@ -463,7 +560,6 @@ struct tts_hip_backend {
     int gemv_dbg = 0;
     // Q4_K GEMVs in the lane layout run the unique-load kernel (k_gemv_q4_K_u) where the shape fits
     int gemv_unique = 1;
-    int gemm_q8 = 1;    // TTS_HIP_OPT_GEMM_Q8
     int64_t cus = 256;  // compute units this backend's stream may use (TTS_HIP_OPT_CU_PARTITION); grids are sized to it
     int cu_total = 256;
     int bgemm_f32 = 1;  // TTS_HIP_OPT_BGEMM_F32
@@ -477,17 +573,14 @@ struct tts_hip_backend {
     int gemv_kr_loop = 1;      // TTS_HIP_OPT_GEMV_KRELAY_LOOP
     int gemv_kr_tail = 1;      // TTS_HIP_OPT_GEMV_KR_TAIL (0 .. 4; GemvJob::kr_tail carries its KR_TAIL_* bits)
     int gemv_q80_pro = 1;      // TTS_HIP_OPT_GEMV_Q80_PRO
-    int gemv_q80_slab = 1;     // TTS_HIP_OPT_GEMV_Q80_SLAB
-    int gemv_q80_rw = 0;       // TTS_HIP_OPT_GEMV_Q80_RW
-    int gemm_q8_staged = 2;    // TTS_HIP_OPT_GEMM_Q8_STAGED
-    int gemv_q50_slab = 1;     // TTS_HIP_OPT_GEMV_Q50_SLAB
-    int gemv_q50_rw = 0;       // TTS_HIP_OPT_GEMV_Q50_RW
-    int gemm_q5 = 1;           // TTS_HIP_OPT_GEMM_Q5
-    int gemm_q5_staged = 2;    // TTS_HIP_OPT_GEMM_Q5_STAGED
-    int gemv_q40_slab = 1;     // TTS_HIP_OPT_GEMV_Q40_SLAB
-    int gemv_q40_rw = 0;       // TTS_HIP_OPT_GEMV_Q40_RW
-    int gemm_q4_0 = 1;         // TTS_HIP_OPT_GEMM_Q4_0
-    int gemm_q4_0_staged = 2;  // TTS_HIP_OPT_GEMM_Q4_0_STAGED
+    // the Q8_0 / Q5_0 / Q4_0 kernels' options, one record per format at b32_index(wtype)
+    struct B32Opts {
+        int slab = 1;    // TTS_HIP_OPT_GEMV_Q80_SLAB / _Q50_SLAB / _Q40_SLAB
+        int rw = 0;      // TTS_HIP_OPT_GEMV_Q80_RW / _Q50_RW / _Q40_RW
+        int gemm = 1;    // TTS_HIP_OPT_GEMM_Q8 / _Q5 / _Q4_0
+        int staged = 2;  // TTS_HIP_OPT_GEMM_Q8_STAGED / _Q5_STAGED / _Q4_0_STAGED
+    };
+    std::array<B32Opts, 3> b32;
     int64_t gemv_kr_ink = 0;   // TTS_HIP_OPT_GEMV_KR_INKERNEL (max K)
     int gemm_kr_walk = 0;      // TTS_HIP_OPT_GEMM_KR_WALK: row-tile walkers per column tile of a many-column GEMM
     int gemm_pf = 64;          // TTS_HIP_OPT_GEMM_PF: many-column Q4_K products of >= value columns on k_gemm_q4K_pf (0 = off)

@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256) void k_lstm_step(LstmStepArgs a0, LstmStepArgs
     a.h[u] = __fmul_rn(cr_tanhf(c), go);
 }
 
-// The step for Q8_0 / Q5_0 / Q4_0 recurrent weights (WT).  ggml's MUL_MAT quantizes h_prev to Q8_0
+// The step for Q8_0 / Q5_0 / Q4_0 recurrent weights (F, a block trait of hip_internal.h).  ggml's MUL_MAT quantizes h_prev to Q8_0
 // (quantize_row_q8_0 per 32 elements) and folds, per gate row, the blocks in ascending order from 0.0f:
 //   sumf += (float)sumi * (d_w * d_x)      sumi the exact int32 dot, every operation rounded to f32
 // (Q5_0: (d_w * d_x) * (float)sumi with quants q - 16, the same bits; Q4_0: ((float)sumi * d_w) * d_x with quants
@@ -141,12 +141,11 @@ __global__ __launch_bounds__(256) void k_lstm_step(LstmStepArgs a0, LstmStepArgs
 //   5. the tail of k_lstm_step.
 // K <= kLstmQMaxK = 512: 16 blocks, so that the 4 nb items fit the 64 lanes of the unit's wave and the
 // quantized h_prev takes 512 + 64 bytes of LDS; longer rows stay with the generic nodes.
-template <int WT>
+template <class F>
 __global__ __launch_bounds__(256) void k_lstm_step_q(LstmStepArgs a0, LstmStepArgs a1) {
     __shared__ __attribute__((aligned(16))) int8_t xq_s[kLstmQMaxK];
     __shared__ float xd_s[kLstmQMaxK / QK8_0];
-    constexpr int BS = WT == TTS_TYPE_Q8_0 ? 34 : WT == TTS_TYPE_Q5_0 ? 22 : 18;  // block bytes
-    constexpr int ND = WT == TTS_TYPE_Q8_0 ? 8 : WT == TTS_TYPE_Q5_0 ? 5 : 4;     // dwords beside the 16-bit word
+    constexpr int BS = F::BYTES, ND = F::ND;  // block bytes; dwords beside the 16-bit word
     // by value: the members are then scalar loads chosen by the (uniform) chain, and a lane's gate picks among
     // registers; through a reference each lane would first load its gate's pointers from the argument block
     const LstmStepArgs a = blockIdx.y ? a1 : a0;
@@ -185,30 +184,15 @@ __global__ __launch_bounds__(256) void k_lstm_step_q(LstmStepArgs a0, LstmStepAr
     }
     __syncthreads();
     // the block's scale and its 32 int8 weights
-    uint32_t q[ND];  // Q8_0: the quants; Q5_0: qh, qs[0 .. 3]; Q4_0: qs[0 .. 3]
+    uint32_t q[ND];  // the payload dwords
 #pragma unroll
     for (int k = 0; k < ND; ++k) q[k] = odd ? dw[k] : __builtin_amdgcn_alignbit(dw[k + 1], dw[k], 16);
     const float d_w = dev_fp16_to_fp32((uint16_t)((odd ? dw[ND] : dw[0]) & 0xFFFFu));
     int wv[8];
-    if constexpr (WT == TTS_TYPE_Q8_0) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) wv[k] = (int)q[k];
-    } else if constexpr (WT == TTS_TYPE_Q5_0) {
-        const uint32_t qs[4] = {q[1], q[2], q[3], q[4]};
-        q50_unpack(q[0], qs, wv);
-    } else {
-        const uint32_t qs[4] = {q[0], q[1], q[2], q[3]};
-        q40_unpack(qs, wv);
-    }
+    F::unpack(q, wv);
     const int4 * xb = (const int4 *)(xq_s + b * QK8_0);
     const int sumi = q50_dot(wv, xb[0], xb[1]);
-    float term;
-    if constexpr (WT == TTS_TYPE_Q4_0) {
-        term = q40_term(sumi, d_w, xd_s[b]);
-    } else {
-        const float dd = __fmul_rn(d_w, xd_s[b]);
-        term = WT == TTS_TYPE_Q8_0 ? __fmul_rn((float)sumi, dd) : __fmul_rn(dd, (float)sumi);
-    }
+    const float term = F::term(sumi, d_w, xd_s[b]);
     // all kLstmQMaxK / 32 exchanges are issued before the first add (a loop to nb would wait for each in turn)
     float tk[kLstmQMaxK / QK8_0];
 #pragma unroll
@@ -228,9 +212,9 @@ __global__ __launch_bounds__(256) void k_lstm_step_q(LstmStepArgs a0, LstmStepAr
 
 void launch_lstm_step(tts_hip_backend * be, const LstmStepArgs & a, const LstmStepArgs * b) {
     const dim3 grid((unsigned)((a.Hd + 3) / 4), b ? 2u : 1u);
-    if (a.wtype == TTS_TYPE_Q8_0) hipLaunchKernelGGL(k_lstm_step_q<TTS_TYPE_Q8_0>, grid, dim3(256), 0, be->stream, a, b ? *b : a);
-    else if (a.wtype == TTS_TYPE_Q5_0) hipLaunchKernelGGL(k_lstm_step_q<TTS_TYPE_Q5_0>, grid, dim3(256), 0, be->stream, a, b ? *b : a);
-    else if (a.wtype == TTS_TYPE_Q4_0) hipLaunchKernelGGL(k_lstm_step_q<TTS_TYPE_Q4_0>, grid, dim3(256), 0, be->stream, a, b ? *b : a);
+    if (a.wtype == TTS_TYPE_Q8_0) hipLaunchKernelGGL(k_lstm_step_q<BlkQ8_0>, grid, dim3(256), 0, be->stream, a, b ? *b : a);
+    else if (a.wtype == TTS_TYPE_Q5_0) hipLaunchKernelGGL(k_lstm_step_q<BlkQ5_0>, grid, dim3(256), 0, be->stream, a, b ? *b : a);
+    else if (a.wtype == TTS_TYPE_Q4_0) hipLaunchKernelGGL(k_lstm_step_q<BlkQ4_0>, grid, dim3(256), 0, be->stream, a, b ? *b : a);
     else hipLaunchKernelGGL(k_lstm_step, grid, dim3(256), 0, be->stream, a, b ? *b : a);
     TTS_HIP_CHECK(hipGetLastError());
 }

@@ -1998,39 +1998,42 @@ void launch_gemv_q4K_xattn(tts_hip_backend * be, const GemvJob & j, const XAttnA
     TTS_HIP_CHECK(hipGetLastError());
 }
 
-// Q8_0 x Q8_0 GEMV reproducing ggml_vec_dot_q8_0_q8_0's generic order: per (row, column),
-// blocks in ascending order, sumf += (float)sumi * (d_w * d_x).  Phase 1: a thread per
-// (row, block) computes the exact int dots for every column -> LDS; phase 2: a lane per
-// (row, column) folds its blocks in order.
+// ------------------------------------------------------------------------------------------
+// Q8_0 / Q5_0 / Q4_0 x Q8_0 GEMV (the 32-weight formats F = BlkQ8_0, BlkQ5_0, BlkQ4_0 of hip_internal.h),
+// reproducing ggml_vec_dot_<F>_q8_0's generic order: per (row, column), blocks in ascending order,
+// sumf += term_b from 0, with sumi_b the exact int32 dot of the block's 32 int8 weights (Q5_0: q - 16, Q4_0: q - 8)
+// with the activation's int8 and term_b = F::term: (float)sumi * (d_w * d_x), for Q4_0 ((float)sumi * d_w) * d_x.
+// A Q5_0 or Q4_0 block is the Q8_0 block of the same d once its int8 weights stand in registers (F::unpack), so
+// one body serves the three.
+//
+// The general form (K % 32 == 0, any 2-B alignment, <= 8 columns).  Phase 1: a thread per (row, block) computes
+// the term of every column -> LDS; phase 2: a lane per (row, column) adds its blocks' terms in order.  A native
+// block comes as F::BYTES / 2 16-bit loads.
 // PRO (PRO_QUANT / PRO_LN): the workgroup quantizes (after RMS / LayerNorm) the f32 activation itself
 // (q4k_prologue with Q8_0 output: quantize_row_q8_0 per 32 elements, K % 256 == 0), with this thread's
 // first (row, block) weights requested before it; PRO = 0: the activation was quantized by
 // k_quantize_q8_0 (j.aq).  One launch instead of norm + quantize + GEMV.
-template <int MC, int PRO = 0>
-__global__ __launch_bounds__(256) void k_gemv_q8_0(GemvJob j, int RW) {
+// LDS: xq al16(MC*K) | xd al16(4*MC*nb) | terms 4*RW*MC*nb (+ the prologue's trash slots).
+template <class F, int MC, int PRO = 0>
+__global__ __launch_bounds__(256) void k_gemv_b32(GemvJob j, int RW) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int nb = (int)(j.K / QK8_0);
     const int mat = blockIdx.y;
     const uint8_t * __restrict__ W = j.W[mat];
-    float * Y = j.Y[mat];
     const int64_t row0 = (int64_t)blockIdx.x * RW;
     const int rows = (int)((j.N - row0) < RW ? (j.N - row0) : RW);
     const int M = j.M;
     int8_t * xq_s = (int8_t *)smem;
     float * xd_s = (float *)(smem + al16((size_t)MC * j.K + (PRO ? QK_K : 0)));  // + the prologue's trash slot
-    int * s_s = (int *)((char *)xd_s + al16(sizeof(float) * (MC * nb + (PRO ? QK_K / QK8_0 : 0))));
-    float * f_s = (float *)((char *)s_s + al16(sizeof(int) * (size_t)RW * nb * MC));
+    float * T = (float *)((char *)xd_s + al16(sizeof(float) * (MC * nb + (PRO ? QK_K / QK8_0 : 0))));
     const int npairs = rows * nb;
     // this thread's first (row, block): weights in registers before the prologue (clamped, unconditional)
-    int wv0[8];
+    uint32_t q0[F::ND];
     uint16_t dw0;
     {
         const int p = min((int)threadIdx.x, npairs - 1);
         const int r = p / nb, b = p % nb;
-        const uint16_t * bp = (const uint16_t *)(W + (row0 + r) * j.w_row_bytes + (int64_t)b * 34);
-        dw0 = *gptr(bp);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) wv0[k] = (int)*gptr(bp + 1 + 2 * k) | ((int)*gptr(bp + 2 + 2 * k) << 16);
+        b32_load<F>(gptr((const uint16_t *)(W + (row0 + r) * j.w_row_bytes + (int64_t)b * F::BYTES)), dw0, q0);
     }
     TTS_PIN_LOADS();
     if constexpr (PRO != 0) {
@@ -2045,34 +2048,23 @@ __global__ __launch_bounds__(256) void k_gemv_q8_0(GemvJob j, int RW) {
     __syncthreads();
     for (int p = threadIdx.x; p < npairs; p += 256) {
         const int r = p / nb, b = p % nb;
-        float dw;
-        int wv[8];
+        uint32_t q[F::ND];
+        uint16_t dh;
         if (p == (int)threadIdx.x) {
-            dw = dev_fp16_to_fp32(dw0);
+            dh = dw0;
 #pragma unroll
-            for (int k = 0; k < 8; ++k) wv[k] = wv0[k];
+            for (int k = 0; k < F::ND; ++k) q[k] = q0[k];
         } else {
-            const uint16_t * bp = (const uint16_t *)(W + (row0 + r) * j.w_row_bytes + (int64_t)b * 34);
-            dw = dev_fp16_to_fp32(bp[0]);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) wv[k] = (int)bp[1 + 2 * k] | ((int)bp[2 + 2 * k] << 16);
+            b32_load<F>((const uint16_t *)(W + (row0 + r) * j.w_row_bytes + (int64_t)b * F::BYTES), dh, q);
         }
+        const float dw = dev_fp16_to_fp32(dh);
+        int wv[8];
+        F::unpack(q, wv);
 #pragma unroll
         for (int m = 0; m < MC; ++m) {
             if (m >= M) break;
             const int4 * xb = (const int4 *)(xq_s + (m * nb + b) * QK8_0);
-            const int4 x0 = xb[0], x1 = xb[1];
-            int s = __builtin_amdgcn_sdot4(wv[0], x0.x, 0, false);
-            s = __builtin_amdgcn_sdot4(wv[1], x0.y, s, false);
-            s = __builtin_amdgcn_sdot4(wv[2], x0.z, s, false);
-            s = __builtin_amdgcn_sdot4(wv[3], x0.w, s, false);
-            s = __builtin_amdgcn_sdot4(wv[4], x1.x, s, false);
-            s = __builtin_amdgcn_sdot4(wv[5], x1.y, s, false);
-            s = __builtin_amdgcn_sdot4(wv[6], x1.z, s, false);
-            s = __builtin_amdgcn_sdot4(wv[7], x1.w, s, false);
-            const int o = (r * MC + m) * nb + b;
-            s_s[o] = s;
-            f_s[o] = __fmul_rn(dw, xd_s[m * nb + b]);
+            T[(r * MC + m) * nb + b] = F::term(q50_dot(wv, xb[0], xb[1]), dw, xd_s[m * nb + b]);
         }
     }
     __syncthreads();
@@ -2081,24 +2073,25 @@ __global__ __launch_bounds__(256) void k_gemv_q8_0(GemvJob j, int RW) {
         if (m >= M) continue;
         float a = 0.f;
         const int o = (r * MC + m) * nb;
-        for (int b = 0; b < nb; ++b) a = __fadd_rn(a, __fmul_rn((float)s_s[o + b], f_s[o + b]));
+        for (int b = 0; b < nb; ++b) a = __fadd_rn(a, T[o + b]);
         gemv_store<MC>(j, mat, row0 + r, m, a);
     }
 }
 
-// Q8_0 GEMV, slab form (K % 256 == 0, 16-B aligned weights; decode, <= 8 columns).  A workgroup owns RW
+// The slab form (K % 256 == 0, 16-B aligned weights; decode, <= 8 columns).  A workgroup owns RW
 // consecutive rows, i.e. one contiguous RW * row_bytes slab of the matrix: the whole slab is requested
 // up front by LDS-DMA (16 B per lane, fully coalesced, no registers held), so each CU has tens of KB in
 // flight and the launch costs about one memory latency plus slab / per-CU bandwidth, instead of one
-// dependent 34-B block fetch per (row, block) round.  Then, from LDS:
-//   terms: a thread per (row, block pair) -- the pair (2k, 2k+1) spans 68 B at a 4-B aligned offset
-//          (17 dwords; block 2k's quants are the funnel-shifted dwords) -- eight sdot4 per block and
-//          column, term = (float)sumi * (d_w * d_x) as ggml_vec_dot_q8_0_q8_0 rounds it;
+// dependent block fetch per (row, block) round.  Then, from LDS:
+//   terms: a thread per (row, block pair) -- the pair (2k, 2k+1) spans 2 * F::BYTES = 68 / 44 / 36 B at a 4-B
+//          aligned offset (b32_pair: block 2k's payload is the funnel-shifted dwords; the odd dword stride 17 /
+//          11 / 9 keeps a wave's reads on distinct banks) -- eight sdot4 per block and column, then F::term;
 //   chain: a thread per (row, column) adds the nb terms in block order (sumf += term, from 0).
 // So the result is bit-identical to ggml's generic order.  The activation's Q8_0 blocks come from the
 // quantize launch (PRO = 0, DMA'd with the slab) or from the prologue (PRO_QUANT / PRO_LN, whose
 // activation loads are issued before the slab DMA so they do not queue behind it).
-// LDS: slab al1K(RW*row_bytes) | xq al1K(MC*K + 256) | xd al1K(4*(MC*nb + 8)) | terms 4*RW*MC*nb.
+// LDS: slab al1K(RW*row_bytes) | xq al1K(MC*K + 256) | xd al1K(4*(MC*nb + 8)) | terms 4*RW*MC*nb; the Q5_0 and
+// Q4_0 slabs are 22/34 and 18/34 of the Q8_0 one, the rest equal.
 __host__ __device__ constexpr int64_t al1k(int64_t v) { return (v + 1023) & ~(int64_t)1023; }
 // LDS-DMA of `bytes` (a multiple of 16) from 16-B aligned global `src` to LDS `dst`; lanes past the end
 // re-read the last 16 B and land in the 1 KB slack after dst + bytes
@@ -2110,12 +2103,13 @@ __device__ __forceinline__ void dma_span(char * dst, const char * src, int64_t b
         __builtin_amdgcn_global_load_lds(gptr(src + off), (__attribute__((address_space(3))) void *)(dst + (size_t)i * 1024), 16, 0, 0);
     }
 }
-static size_t q80s_lds(int MC, int64_t K, int RW) {
-    const int64_t nb = K / QK8_0, rb = nb * 34;
+template <class F>
+static size_t b32s_lds(int MC, int64_t K, int RW) {
+    const int64_t nb = K / QK8_0, rb = nb * F::BYTES;
     return (size_t)(al1k(RW * rb) + al1k(MC * K + QK_K) + al1k(4 * (MC * nb + 8)) + 4 * (int64_t)RW * MC * nb);
 }
-template <int MC, int PRO = 0>
-__global__ __launch_bounds__(256) void k_gemv_q8_0s(GemvJob j, int RW) {
+template <class F, int MC, int PRO = 0>
+__global__ __launch_bounds__(256) void k_gemv_b32s(GemvJob j, int RW) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nb = (int)(j.K / QK8_0), nbp = nb >> 1;
@@ -2145,201 +2139,13 @@ __global__ __launch_bounds__(256) void k_gemv_q8_0s(GemvJob j, int RW) {
     __syncthreads();
     for (int u = threadIdx.x; u < rows * nbp; u += 256) {
         const int r = u / nbp, k = u - r * nbp;
-        const uint32_t * wl = (const uint32_t *)(ws + r * rb + 68 * k);
-        uint32_t w[17];
+        const uint32_t * wl = (const uint32_t *)(ws + r * rb + 2 * F::BYTES * k);
+        uint32_t w[F::BYTES / 2];
 #pragma unroll
-        for (int i = 0; i < 17; ++i) w[i] = wl[i];
-        const float d0 = dev_fp16_to_fp32((uint16_t)(w[0] & 0xFFFFu));
-        const float d1 = dev_fp16_to_fp32((uint16_t)(w[8] >> 16));
-        int q0[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) q0[i] = (int)__builtin_amdgcn_alignbit(w[i + 1], w[i], 16);
-#pragma unroll
-        for (int m = 0; m < MC; ++m) {
-            if (m >= M) break;
-            const int4 * xb = (const int4 *)(xq_s + (m * nb + 2 * k) * QK8_0);
-            const int4 x0 = xb[0], x1 = xb[1], x2 = xb[2], x3 = xb[3];
-            int s0 = __builtin_amdgcn_sdot4(q0[0], x0.x, 0, false);
-            s0 = __builtin_amdgcn_sdot4(q0[1], x0.y, s0, false);
-            s0 = __builtin_amdgcn_sdot4(q0[2], x0.z, s0, false);
-            s0 = __builtin_amdgcn_sdot4(q0[3], x0.w, s0, false);
-            s0 = __builtin_amdgcn_sdot4(q0[4], x1.x, s0, false);
-            s0 = __builtin_amdgcn_sdot4(q0[5], x1.y, s0, false);
-            s0 = __builtin_amdgcn_sdot4(q0[6], x1.z, s0, false);
-            s0 = __builtin_amdgcn_sdot4(q0[7], x1.w, s0, false);
-            int s1 = __builtin_amdgcn_sdot4((int)w[9], x2.x, 0, false);
-            s1 = __builtin_amdgcn_sdot4((int)w[10], x2.y, s1, false);
-            s1 = __builtin_amdgcn_sdot4((int)w[11], x2.z, s1, false);
-            s1 = __builtin_amdgcn_sdot4((int)w[12], x2.w, s1, false);
-            s1 = __builtin_amdgcn_sdot4((int)w[13], x3.x, s1, false);
-            s1 = __builtin_amdgcn_sdot4((int)w[14], x3.y, s1, false);
-            s1 = __builtin_amdgcn_sdot4((int)w[15], x3.z, s1, false);
-            s1 = __builtin_amdgcn_sdot4((int)w[16], x3.w, s1, false);
-            const float2 xd = *(const float2 *)(xd_s + m * nb + 2 * k);
-            float2 t;
-            t.x = __fmul_rn((float)s0, __fmul_rn(d0, xd.x));
-            t.y = __fmul_rn((float)s1, __fmul_rn(d1, xd.y));
-            *(float2 *)(T + (r * MC + m) * nb + 2 * k) = t;
-        }
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < rows * MC; t += 256) {
-        const int r = t / MC, m = t % MC;
-        if (m >= M) continue;
-        const float4 * tr = (const float4 *)(T + (r * MC + m) * nb);
-        float a = 0.f;
-        for (int b = 0; b < (nb >> 2); ++b) {
-            const float4 v = tr[b];
-            a = __fadd_rn(a, v.x);
-            a = __fadd_rn(a, v.y);
-            a = __fadd_rn(a, v.z);
-            a = __fadd_rn(a, v.w);
-        }
-        gemv_store<MC>(j, mat, row0 + r, m, a);
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// Q5_0 x Q8_0 (ggml_vec_dot_q5_0_q8_0, generic order): per (row, column), blocks ascending,
-// sumf += (float)sumi * (d_w * d_x), sumi the exact int32 dot of the block's 32 weights q - 16 in
-// [-16, 15] with the activation's int8.  A Q5_0 block {f16 d; u8 qh[4]; u8 qs[16]} is the Q8_0 block
-// of the same d whose quants are q - 16, and ggml_vec_dot_q8_0_q8_0 rounds the same three operations
-// in the same order, so the Q8_0 kernels' arithmetic applies once the int8 weights stand in registers.
-// The unpack (q50_unpack) and the block dot (q50_dot) stand in hip_internal.h: the fused LSTM step uses them too.
-
-// The general form (K % 32 == 0, any alignment, <= 8 columns), k_gemv_q8_0's structure: a thread per
-// (row, block) computes the exact int dots for every column -> LDS, then a lane per (row, column)
-// folds its blocks in order.  Native blocks are 22 B at a 2-B aligned address: eleven 16-bit loads.
-// PRO as k_gemv_q8_0 (the activation is the same Q8_0).
-template <int MC, int PRO = 0>
-__global__ __launch_bounds__(256) void k_gemv_q5_0(GemvJob j, int RW) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int nb = (int)(j.K / QK5_0);
-    const int mat = blockIdx.y;
-    const uint8_t * __restrict__ W = j.W[mat];
-    const int64_t row0 = (int64_t)blockIdx.x * RW;
-    const int rows = (int)((j.N - row0) < RW ? (j.N - row0) : RW);
-    const int M = j.M;
-    int8_t * xq_s = (int8_t *)smem;
-    float * xd_s = (float *)(smem + al16((size_t)MC * j.K + (PRO ? QK_K : 0)));  // + the prologue's trash slot
-    int * s_s = (int *)((char *)xd_s + al16(sizeof(float) * (MC * nb + (PRO ? QK_K / QK8_0 : 0))));
-    float * f_s = (float *)((char *)s_s + al16(sizeof(int) * (size_t)RW * nb * MC));
-    const int npairs = rows * nb;
-    // this thread's first (row, block): its 22 bytes in registers before the prologue (clamped, unconditional)
-    uint16_t h0[11];
-    {
-        const int p = min((int)threadIdx.x, npairs - 1);
-        const int r = p / nb, b = p % nb;
-        const uint16_t * bp = (const uint16_t *)(W + (row0 + r) * j.w_row_bytes + (int64_t)b * 22);
-#pragma unroll
-        for (int k = 0; k < 11; ++k) h0[k] = *gptr(bp + k);
-    }
-    TTS_PIN_LOADS();
-    if constexpr (PRO != 0) {
-        q4k_prologue<PRO, 16, false, NoMid, true>(j, (int)(j.K / QK_K), xq_s, xd_s, nullptr);
-    } else {
-        const int4 * src = (const int4 *)j.aq.qs;
-        int4 * dst = (int4 *)xq_s;
-        const int n16 = (int)((int64_t)M * j.K / 16);
-        for (int i = threadIdx.x; i < n16; i += 256) dst[i] = src[i];
-        for (int i = threadIdx.x; i < M * nb; i += 256) xd_s[i] = j.aq.d[i];
-    }
-    __syncthreads();
-    for (int p = threadIdx.x; p < npairs; p += 256) {
-        const int r = p / nb, b = p % nb;
-        uint16_t h[11];
-        if (p == (int)threadIdx.x) {
-#pragma unroll
-            for (int k = 0; k < 11; ++k) h[k] = h0[k];
-        } else {
-            const uint16_t * bp = (const uint16_t *)(W + (row0 + r) * j.w_row_bytes + (int64_t)b * 22);
-#pragma unroll
-            for (int k = 0; k < 11; ++k) h[k] = bp[k];
-        }
-        const float dw = dev_fp16_to_fp32(h[0]);
-        uint32_t qs[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) qs[k] = (uint32_t)h[3 + 2 * k] | ((uint32_t)h[4 + 2 * k] << 16);
-        int wv[8];
-        q50_unpack((uint32_t)h[1] | ((uint32_t)h[2] << 16), qs, wv);
-#pragma unroll
-        for (int m = 0; m < MC; ++m) {
-            if (m >= M) break;
-            const int4 * xb = (const int4 *)(xq_s + (m * nb + b) * QK8_0);
-            const int o = (r * MC + m) * nb + b;
-            s_s[o] = q50_dot(wv, xb[0], xb[1]);
-            f_s[o] = __fmul_rn(dw, xd_s[m * nb + b]);
-        }
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < rows * MC; t += 256) {
-        const int r = t / MC, m = t % MC;
-        if (m >= M) continue;
-        float a = 0.f;
-        const int o = (r * MC + m) * nb;
-        for (int b = 0; b < nb; ++b) a = __fadd_rn(a, __fmul_rn((float)s_s[o + b], f_s[o + b]));
-        gemv_store<MC>(j, mat, row0 + r, m, a);
-    }
-}
-
-// The slab form (K % 256 == 0, 16-B aligned weights, <= 8 columns), k_gemv_q8_0s's structure: rows are
-// 176 K / 256 bytes (a multiple of 16), the workgroup's RW rows come whole by LDS-DMA, then from LDS
-//   terms: a thread per (row, block pair) -- the pair (2k, 2k+1) spans 44 B at a 4-B aligned offset (11
-//          dwords: d0 | qh0 lo, qh0 hi | qs0 .., .. qs0 | d1, qh1, qs1 x 4; block 2k's qh and qs are the
-//          funnel-shifted dwords; the odd dword stride keeps a wave's reads on distinct banks);
-//   chain: a thread per (row, column) adds the nb terms in block order.
-// LDS: slab al1K(RW*row_bytes) | xq al1K(MC*K + 256) | xd al1K(4*(MC*nb + 8)) | terms 4*RW*MC*nb --
-// 22/34 of the Q8_0 slab, the rest equal.
-static size_t q50s_lds(int MC, int64_t K, int RW) {
-    const int64_t nb = K / QK5_0, rb = nb * 22;
-    return (size_t)(al1k(RW * rb) + al1k(MC * K + QK_K) + al1k(4 * (MC * nb + 8)) + 4 * (int64_t)RW * MC * nb);
-}
-template <int MC, int PRO = 0>
-__global__ __launch_bounds__(256) void k_gemv_q5_0s(GemvJob j, int RW) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nb = (int)(j.K / QK5_0), nbp = nb >> 1;
-    const int64_t rb = j.w_row_bytes;
-    const int mat = blockIdx.y;
-    const int64_t row0 = (int64_t)blockIdx.x * RW;
-    const int rows = (int)((j.N - row0) < RW ? (j.N - row0) : RW);
-    const int M = j.M;
-    char * ws = smem;
-    int8_t * xq_s = (int8_t *)(smem + al1k(RW * rb));
-    float * xd_s = (float *)((char *)xq_s + al1k(MC * j.K + QK_K));
-    float * T = (float *)((char *)xd_s + al1k(4 * (MC * nb + 8)));
-    const char * slab = (const char *)j.W[mat] + row0 * rb;
-    auto dma_slab = [&]() { dma_span(ws, slab, rows * rb, wave, 4, lane); };
-    if constexpr (PRO != 0) {
-        struct Mid {
-            decltype(dma_slab) & f;
-            __device__ void operator()() const { f(); }
-        };
-        q4k_prologue<PRO, 16, false, Mid, true>(j, (int)(j.K / QK_K), xq_s, xd_s, nullptr, nullptr, nullptr, Mid{dma_slab});
-    } else {
-        dma_slab();
-        dma_span((char *)xq_s, (const char *)j.aq.qs, (int64_t)M * j.K, wave, 4, lane);
-        dma_span((char *)xd_s, (const char *)j.aq.d, (int64_t)4 * M * nb, wave, 4, lane);
-    }
-    __builtin_amdgcn_s_waitcnt(0);  // this wave's DMA has landed (vmcnt, lgkmcnt 0)
-    __syncthreads();
-    for (int u = threadIdx.x; u < rows * nbp; u += 256) {
-        const int r = u / nbp, k = u - r * nbp;
-        const uint32_t * wl = (const uint32_t *)(ws + r * rb + 44 * k);
-        uint32_t w[11];
-#pragma unroll
-        for (int i = 0; i < 11; ++i) w[i] = wl[i];
-        const float d0 = dev_fp16_to_fp32((uint16_t)(w[0] & 0xFFFFu));
-        const float d1 = dev_fp16_to_fp32((uint16_t)(w[5] >> 16));
-        uint32_t qs0[4], qs1[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            qs0[i] = __builtin_amdgcn_alignbit(w[i + 2], w[i + 1], 16);
-            qs1[i] = w[7 + i];
-        }
+        for (int i = 0; i < F::BYTES / 2; ++i) w[i] = wl[i];
+        float d0, d1;
         int q0[8], q1[8];
-        q50_unpack(__builtin_amdgcn_alignbit(w[1], w[0], 16), qs0, q0);
-        q50_unpack(w[6], qs1, q1);
+        b32_pair<F>(w, d0, d1, q0, q1);
 #pragma unroll
         for (int m = 0; m < MC; ++m) {
             if (m >= M) break;
@@ -2348,8 +2154,8 @@ __global__ __launch_bounds__(256) void k_gemv_q5_0s(GemvJob j, int RW) {
             const int s1 = q50_dot(q1, xb[2], xb[3]);
             const float2 xd = *(const float2 *)(xd_s + m * nb + 2 * k);
             float2 t;
-            t.x = __fmul_rn((float)s0, __fmul_rn(d0, xd.x));
-            t.y = __fmul_rn((float)s1, __fmul_rn(d1, xd.y));
+            t.x = F::term(s0, d0, xd.x);
+            t.y = F::term(s1, d1, xd.y);
             *(float2 *)(T + (r * MC + m) * nb + 2 * k) = t;
         }
     }
@@ -2370,173 +2176,6 @@ __global__ __launch_bounds__(256) void k_gemv_q5_0s(GemvJob j, int RW) {
     }
 }
 
-// ------------------------------------------------------------------------------------------
-// Q4_0 x Q8_0 (ggml_vec_dot_q4_0_q8_0, generic order): per (row, column), blocks ascending,
-// sumf += ((float)sumi * d_w) * d_x, sumi the exact int32 dot of the block's 32 weights q - 8 in [-8, 7] with
-// the activation's int8.  The association differs from Q8_0's and Q5_0's sumi * (d_w * d_x), so these kernels
-// keep d_w and d_x apart until the term (q40_term); everything else is the Q5_0 kernels' structure with an
-// 18-B block {f16 d; u8 qs[16]} and a shorter unpack (q40_unpack, hip_internal.h).
-
-// The general form (K % 32 == 0, any alignment, <= 8 columns): a thread per (row, block) computes the term of
-// every column -> LDS, then a lane per (row, column) adds its blocks' terms in order.  Native blocks are 18 B
-// at a 2-B aligned address: nine 16-bit loads.  PRO as k_gemv_q8_0 (the activation is the same Q8_0).  The LDS
-// layout is k_gemv_q8_0's (q80_lds); the terms take its f32 array, the int array stays unused.
-template <int MC, int PRO = 0>
-__global__ __launch_bounds__(256) void k_gemv_q4_0(GemvJob j, int RW) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int nb = (int)(j.K / QK4_0);
-    const int mat = blockIdx.y;
-    const uint8_t * __restrict__ W = j.W[mat];
-    const int64_t row0 = (int64_t)blockIdx.x * RW;
-    const int rows = (int)((j.N - row0) < RW ? (j.N - row0) : RW);
-    const int M = j.M;
-    int8_t * xq_s = (int8_t *)smem;
-    float * xd_s = (float *)(smem + al16((size_t)MC * j.K + (PRO ? QK_K : 0)));  // + the prologue's trash slot
-    int * s_s = (int *)((char *)xd_s + al16(sizeof(float) * (MC * nb + (PRO ? QK_K / QK8_0 : 0))));
-    float * f_s = (float *)((char *)s_s + al16(sizeof(int) * (size_t)RW * nb * MC));
-    const int npairs = rows * nb;
-    // this thread's first (row, block): its 18 bytes in registers before the prologue (clamped, unconditional)
-    uint16_t h0[9];
-    {
-        const int p = min((int)threadIdx.x, npairs - 1);
-        const int r = p / nb, b = p % nb;
-        const uint16_t * bp = (const uint16_t *)(W + (row0 + r) * j.w_row_bytes + (int64_t)b * 18);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) h0[k] = *gptr(bp + k);
-    }
-    TTS_PIN_LOADS();
-    if constexpr (PRO != 0) {
-        q4k_prologue<PRO, 16, false, NoMid, true>(j, (int)(j.K / QK_K), xq_s, xd_s, nullptr);
-    } else {
-        const int4 * src = (const int4 *)j.aq.qs;
-        int4 * dst = (int4 *)xq_s;
-        const int n16 = (int)((int64_t)M * j.K / 16);
-        for (int i = threadIdx.x; i < n16; i += 256) dst[i] = src[i];
-        for (int i = threadIdx.x; i < M * nb; i += 256) xd_s[i] = j.aq.d[i];
-    }
-    __syncthreads();
-    for (int p = threadIdx.x; p < npairs; p += 256) {
-        const int r = p / nb, b = p % nb;
-        uint16_t h[9];
-        if (p == (int)threadIdx.x) {
-#pragma unroll
-            for (int k = 0; k < 9; ++k) h[k] = h0[k];
-        } else {
-            const uint16_t * bp = (const uint16_t *)(W + (row0 + r) * j.w_row_bytes + (int64_t)b * 18);
-#pragma unroll
-            for (int k = 0; k < 9; ++k) h[k] = bp[k];
-        }
-        const float dw = dev_fp16_to_fp32(h[0]);
-        uint32_t qs[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) qs[k] = (uint32_t)h[1 + 2 * k] | ((uint32_t)h[2 + 2 * k] << 16);
-        int wv[8];
-        q40_unpack(qs, wv);
-#pragma unroll
-        for (int m = 0; m < MC; ++m) {
-            if (m >= M) break;
-            const int4 * xb = (const int4 *)(xq_s + (m * nb + b) * QK8_0);
-            f_s[(r * MC + m) * nb + b] = q40_term(q50_dot(wv, xb[0], xb[1]), dw, xd_s[m * nb + b]);
-        }
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < rows * MC; t += 256) {
-        const int r = t / MC, m = t % MC;
-        if (m >= M) continue;
-        float a = 0.f;
-        const int o = (r * MC + m) * nb;
-        for (int b = 0; b < nb; ++b) a = __fadd_rn(a, f_s[o + b]);
-        gemv_store<MC>(j, mat, row0 + r, m, a);
-    }
-}
-
-// The slab form (K % 256 == 0, 16-B aligned weights, <= 8 columns), k_gemv_q5_0s's structure: rows are
-// 144 K / 256 bytes (a multiple of 16), the workgroup's RW rows come whole by LDS-DMA, then from LDS
-//   terms: a thread per (row, block pair) -- the pair (2k, 2k+1) spans 36 B at a 4-B aligned offset (9
-//          dwords: d0 | qs0 .., .. qs0 | d1, qs1 x 4; block 2k's qs are the funnel-shifted dwords; the odd
-//          dword stride keeps a wave's reads on distinct banks);
-//   chain: a thread per (row, column) adds the nb terms in block order.
-// LDS: slab al1K(RW*row_bytes) | xq al1K(MC*K + 256) | xd al1K(4*(MC*nb + 8)) | terms 4*RW*MC*nb --
-// 18/34 of the Q8_0 slab, the rest equal.
-static size_t q40s_lds(int MC, int64_t K, int RW) {
-    const int64_t nb = K / QK4_0, rb = nb * 18;
-    return (size_t)(al1k(RW * rb) + al1k(MC * K + QK_K) + al1k(4 * (MC * nb + 8)) + 4 * (int64_t)RW * MC * nb);
-}
-template <int MC, int PRO = 0>
-__global__ __launch_bounds__(256) void k_gemv_q4_0s(GemvJob j, int RW) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nb = (int)(j.K / QK4_0), nbp = nb >> 1;
-    const int64_t rb = j.w_row_bytes;
-    const int mat = blockIdx.y;
-    const int64_t row0 = (int64_t)blockIdx.x * RW;
-    const int rows = (int)((j.N - row0) < RW ? (j.N - row0) : RW);
-    const int M = j.M;
-    char * ws = smem;
-    int8_t * xq_s = (int8_t *)(smem + al1k(RW * rb));
-    float * xd_s = (float *)((char *)xq_s + al1k(MC * j.K + QK_K));
-    float * T = (float *)((char *)xd_s + al1k(4 * (MC * nb + 8)));
-    const char * slab = (const char *)j.W[mat] + row0 * rb;
-    auto dma_slab = [&]() { dma_span(ws, slab, rows * rb, wave, 4, lane); };
-    if constexpr (PRO != 0) {
-        struct Mid {
-            decltype(dma_slab) & f;
-            __device__ void operator()() const { f(); }
-        };
-        q4k_prologue<PRO, 16, false, Mid, true>(j, (int)(j.K / QK_K), xq_s, xd_s, nullptr, nullptr, nullptr, Mid{dma_slab});
-    } else {
-        dma_slab();
-        dma_span((char *)xq_s, (const char *)j.aq.qs, (int64_t)M * j.K, wave, 4, lane);
-        dma_span((char *)xd_s, (const char *)j.aq.d, (int64_t)4 * M * nb, wave, 4, lane);
-    }
-    __builtin_amdgcn_s_waitcnt(0);  // this wave's DMA has landed (vmcnt, lgkmcnt 0)
-    __syncthreads();
-    for (int u = threadIdx.x; u < rows * nbp; u += 256) {
-        const int r = u / nbp, k = u - r * nbp;
-        const uint32_t * wl = (const uint32_t *)(ws + r * rb + 36 * k);
-        uint32_t w[9];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) w[i] = wl[i];
-        const float d0 = dev_fp16_to_fp32((uint16_t)(w[0] & 0xFFFFu));
-        const float d1 = dev_fp16_to_fp32((uint16_t)(w[4] >> 16));
-        uint32_t qs0[4], qs1[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            qs0[i] = __builtin_amdgcn_alignbit(w[i + 1], w[i], 16);
-            qs1[i] = w[5 + i];
-        }
-        int q0[8], q1[8];
-        q40_unpack(qs0, q0);
-        q40_unpack(qs1, q1);
-#pragma unroll
-        for (int m = 0; m < MC; ++m) {
-            if (m >= M) break;
-            const int4 * xb = (const int4 *)(xq_s + (m * nb + 2 * k) * QK8_0);
-            const int s0 = q50_dot(q0, xb[0], xb[1]);
-            const int s1 = q50_dot(q1, xb[2], xb[3]);
-            const float2 xd = *(const float2 *)(xd_s + m * nb + 2 * k);
-            float2 t;
-            t.x = q40_term(s0, d0, xd.x);
-            t.y = q40_term(s1, d1, xd.y);
-            *(float2 *)(T + (r * MC + m) * nb + 2 * k) = t;
-        }
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < rows * MC; t += 256) {
-        const int r = t / MC, m = t % MC;
-        if (m >= M) continue;
-        const float4 * tr = (const float4 *)(T + (r * MC + m) * nb);
-        float a = 0.f;
-        for (int b = 0; b < (nb >> 2); ++b) {
-            const float4 v = tr[b];
-            a = __fadd_rn(a, v.x);
-            a = __fadd_rn(a, v.y);
-            a = __fadd_rn(a, v.z);
-            a = __fadd_rn(a, v.w);
-        }
-        gemv_store<MC>(j, mat, row0 + r, m, a);
-    }
-}
 
 // F32 / F16 GEMV: f32 products, f64 accumulation (ggml_vec_dot_f32 / _f16 generic), a wave per
 // row, 16-B loads.  For F16 the activation was rounded to fp16 first (vec_dot_type F16).
@@ -2829,11 +2468,22 @@ static void launch_gemv_q4k_mc(tts_hip_backend * be, const GemvJob & j) {
         else launch_q4k<MC, PRO_QUANT, 16>(be, j, (unsigned)gx, (int)nw, lds);
     }
 }
-static size_t q80_lds(int MC, int64_t K, int RW) {
+// General Q8_0 / Q5_0 / Q4_0 GEMV (k_gemv_b32): rows per workgroup and the LDS to request.  This geometry is the
+// parent's tuning, which this kernel's smaller layout does not retune: RW is the largest of 8 / 4 / 2 / 1 whose
+// activation + 8 B per (row, block, column) stays within 64 KB, although the kernel now keeps 4 B of them.
+static int b32_rw(int MC, int64_t K) {
     const int64_t nb = K / QK8_0;
     auto a = [](size_t n) { return (n + 15) & ~(size_t)15; };
-    return a((size_t)MC * K) + a(4 * MC * nb) + a(4 * (size_t)RW * nb * MC) + 4 * (size_t)RW * nb * MC;
+    int RW = 8;
+    while (RW > 1 && a((size_t)MC * K) + a(4 * MC * nb) + a(4 * (size_t)RW * nb * MC) + 4 * (size_t)RW * nb * MC > 64 * 1024) RW /= 2;
+    return RW;
 }
+static size_t b32_lds(int MC, int64_t K, int RW, int pro) {
+    const int64_t nb = K / QK8_0;
+    auto a = [](size_t n) { return (n + 15) & ~(size_t)15; };
+    return a((size_t)MC * K) + a(4 * MC * nb) + 4 * (size_t)RW * nb * MC + (pro ? QK_K + 64 : 0);
+}
+
 
 // ---- MFMA path (k_gemv_q4K_mf) ----
 // + the cross-over buffer: SwiGLU gate results (4 waves x 64 lanes x 4 floats) or the residue-split
@@ -3298,25 +2948,28 @@ static void launch_q4k_ks(tts_hip_backend * be, const GemvJob & j) {
 }
 
 // ------------------------------------------------------------------------------------------
-// Q8_0 x Q8_0 GEMM for many columns (Dia's 1024-position encoder, prompt prefills) on the int8
-// matrix cores.  ggml_vec_dot_q8_0_q8_0 per (row, column): sumf += sumi_b * (d_w,b * d_x,b) over the
-// 32-element blocks b in ascending order, sumi_b the exact int32 dot of the block.  One
+// Q8_0 / Q5_0 / Q4_0 x Q8_0 GEMM for many columns (Dia's 1024-position encoder, prompt prefills) on the int8
+// matrix cores.  ggml_vec_dot_<F>_q8_0 per (row, column): sumf += term_b over the 32-element blocks b in
+// ascending order, term_b = F::term of the exact int32 block dot sumi_b.  One
 // v_mfma_i32_16x16x32_i8 computes sumi_b for a 16 x 16 tile exactly (K = 32 = one block; A[i = l&15]
 // [k = 8(l>>4)..+7], B[k][j = l&15], D col l&15, rows 4(l>>4)+e), and each lane then folds its
 // outputs' terms into f32 sums in block order with ggml's roundings: bit-identical to the GEMV.
 // Workgroup: 4 waves over a 64-row x 64-column tile (2 x 2 MFMA tiles per wave); the next block's
-// operands are loaded before the current block's MFMAs.  Native Q8_0 rows (34-B blocks, 2-B
-// aligned): a lane's 8 weight bytes come as four 16-bit loads; activations are the Q8_0 copy
-// (int8 [M][K], fp16-rounded d [M][K/32]) prepare_act made.
+// operands are loaded before the current block's MFMAs.  Native rows (F::BYTES-B blocks, 2-B aligned): lane
+// group kq's A operand is weights 8 kq .. 8 kq + 7 of the block (b32_octet: eight payload bytes as four 16-bit
+// loads, for Q5_0 the qh byte alone); activations are the Q8_0 copy (int8 [M][K], fp16-rounded d [M][K/32])
+// prepare_act made.  The only route for K % 256 != 0 or 2-B aligned rows.
 typedef int i32x4_t __attribute__((ext_vector_type(4)));
 
-__global__ __launch_bounds__(256) void k_gemm_q8_0(GemvJob j) {
+template <class F>
+__global__ __launch_bounds__(256) void k_gemm_b32(GemvJob j) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int mat = blockIdx.z;
     const int nb = (int)(j.K / QK8_0);
     const int64_t r0 = (int64_t)blockIdx.x * 64 + (wave & 1) * 32;
     const int64_t c0 = (int64_t)blockIdx.y * 64 + (wave >> 1) * 32;
     const int r16 = lane & 15, kq = lane >> 4;
+    const int nsh = F::nsh(kq);
     const uint8_t * W = j.W[mat];
     const uint8_t * wrow[2];
     const int8_t * xcol[2];
@@ -3347,13 +3000,11 @@ __global__ __launch_bounds__(256) void k_gemm_q8_0(GemvJob j) {
     auto load = [&](int b, long (&fa)[2], long (&fb)[2], float (&fw)[2][4], float (&fx)[2]) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            const uint16_t * q = (const uint16_t *)(wrow[t] + (int64_t)b * 34 + 2 + 8 * kq);
-            const uint64_t w = (uint64_t)q[0] | ((uint64_t)q[1] << 16) | ((uint64_t)q[2] << 32) | ((uint64_t)q[3] << 48);
-            fa[t] = (long)w;
+            fa[t] = b32_octet<F>(wrow[t] + (int64_t)b * F::BYTES, kq, nsh);
             fb[t] = *(const long *)(xcol[t] + (int64_t)b * QK8_0 + 8 * kq);
             fx[t] = xd[t][b];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) fw[t][e] = dev_fp16_to_fp32(*(const uint16_t *)(drow[t][e] + (int64_t)b * 34));
+            for (int e = 0; e < 4; ++e) fw[t][e] = dev_fp16_to_fp32(*(const uint16_t *)(drow[t][e] + (int64_t)b * F::BYTES));
         }
     };
     load(0, av, bv, dwv, dxv);
@@ -3366,182 +3017,7 @@ __global__ __launch_bounds__(256) void k_gemm_q8_0(GemvJob j) {
                 const i32x4_t z = {0, 0, 0, 0};
                 const i32x4_t s = __builtin_amdgcn_mfma_i32_16x16x32_i8(av[ti], bv[tj], z, 0, 0, 0);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) acc[ti][tj][e] = __fadd_rn(acc[ti][tj][e], __fmul_rn((float)s[e], __fmul_rn(dwv[ti][e], dxv[tj])));
-            }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            av[t] = an[t], bv[t] = bn[t], dxv[t] = dxn[t];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) dwv[t][e] = dwn[t][e];
-        }
-    }
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj) {
-            const int64_t col = c0 + 16 * tj + r16;
-            if (col >= j.M) continue;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int64_t row = r0 + 16 * ti + 4 * kq + e;
-                if (row < j.N) gemv_store<1>(j, mat, row, (int)col, acc[ti][tj][e]);
-            }
-        }
-}
-
-// Q5_0 x Q8_0 GEMM for many columns: k_gemm_q8_0 with the A operand unpacked from the 22-B block.  Lane
-// group kq holds weights 8 kq .. 8 kq + 7 of the block, paired with the activation's same octet: groups
-// 0, 1 the low nibbles of qs[0..7] / qs[8..15], groups 2, 3 their high nibbles, each with byte kq of qh
-// (q50_himask).  Native rows (2-B aligned): the eight qs bytes as four 16-bit loads, the qh byte alone.
-__global__ __launch_bounds__(256) void k_gemm_q5_0(GemvJob j) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int mat = blockIdx.z;
-    const int nb = (int)(j.K / QK5_0);
-    const int64_t r0 = (int64_t)blockIdx.x * 64 + (wave & 1) * 32;
-    const int64_t c0 = (int64_t)blockIdx.y * 64 + (wave >> 1) * 32;
-    const int r16 = lane & 15, kq = lane >> 4;
-    const int nsh = (kq >> 1) * 4;  // high nibbles for weights 16 .. 31
-    const uint8_t * W = j.W[mat];
-    const uint8_t * wrow[2];
-    const int8_t * xcol[2];
-    const float * xd[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int64_t r = min(r0 + 16 * t + r16, j.N - 1);
-        const int64_t c = min(c0 + 16 * t + r16, j.M - 1);
-        wrow[t] = W + r * j.w_row_bytes;
-        xcol[t] = j.aq.qs + c * j.K;
-        xd[t] = j.aq.d + c * nb;
-    }
-    // rows of this lane's accumulator elements (t, e): r0 + 16 t + 4 kq + e
-    const uint8_t * drow[2][4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) drow[t][e] = W + min(r0 + 16 * t + 4 * kq + e, j.N - 1) * j.w_row_bytes;
-    float acc[2][2][4];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[a][b][e] = 0.0f;
-    long av[2], bv[2], an[2], bn[2];
-    float dwv[2][4], dxv[2], dwn[2][4], dxn[2];
-    auto load = [&](int b, long (&fa)[2], long (&fb)[2], float (&fw)[2][4], float (&fx)[2]) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const uint8_t * blk = wrow[t] + (int64_t)b * 22;
-            const uint16_t * q = (const uint16_t *)(blk + 6 + 8 * (kq & 1));
-            const uint32_t nqh = ~(uint32_t)blk[2 + kq];
-            const uint32_t q0 = (uint32_t)q[0] | ((uint32_t)q[1] << 16), q1 = (uint32_t)q[2] | ((uint32_t)q[3] << 16);
-            const uint32_t lo = ((q0 >> nsh) & 0x0F0F0F0Fu) | q50_himask(nqh, 0);
-            const uint32_t hi = ((q1 >> nsh) & 0x0F0F0F0Fu) | q50_himask(nqh, 4);
-            fa[t] = (long)(((uint64_t)hi << 32) | lo);
-            fb[t] = *(const long *)(xcol[t] + (int64_t)b * QK8_0 + 8 * kq);
-            fx[t] = xd[t][b];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) fw[t][e] = dev_fp16_to_fp32(*(const uint16_t *)(drow[t][e] + (int64_t)b * 22));
-        }
-    };
-    load(0, av, bv, dwv, dxv);
-    for (int b = 0; b < nb; ++b) {
-        if (b + 1 < nb) load(b + 1, an, bn, dwn, dxn);
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj) {
-                const i32x4_t z = {0, 0, 0, 0};
-                const i32x4_t s = __builtin_amdgcn_mfma_i32_16x16x32_i8(av[ti], bv[tj], z, 0, 0, 0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[ti][tj][e] = __fadd_rn(acc[ti][tj][e], __fmul_rn((float)s[e], __fmul_rn(dwv[ti][e], dxv[tj])));
-            }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            av[t] = an[t], bv[t] = bn[t], dxv[t] = dxn[t];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) dwv[t][e] = dwn[t][e];
-        }
-    }
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj) {
-            const int64_t col = c0 + 16 * tj + r16;
-            if (col >= j.M) continue;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int64_t row = r0 + 16 * ti + 4 * kq + e;
-                if (row < j.N) gemv_store<1>(j, mat, row, (int)col, acc[ti][tj][e]);
-            }
-        }
-}
-
-// Q4_0 x Q8_0 GEMM for many columns: k_gemm_q5_0 with the 18-B block, no fifth bit and ggml's Q4_0 term
-// ((float)sumi * d_w) * d_x.  Lane group kq holds weights 8 kq .. 8 kq + 7: groups 0, 1 the low nibbles of
-// qs[0..7] / qs[8..15], groups 2, 3 their high nibbles, each made q - 8 by q40_s8.  Native rows (2-B aligned):
-// the eight qs bytes as four 16-bit loads.
-__global__ __launch_bounds__(256) void k_gemm_q4_0(GemvJob j) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int mat = blockIdx.z;
-    const int nb = (int)(j.K / QK4_0);
-    const int64_t r0 = (int64_t)blockIdx.x * 64 + (wave & 1) * 32;
-    const int64_t c0 = (int64_t)blockIdx.y * 64 + (wave >> 1) * 32;
-    const int r16 = lane & 15, kq = lane >> 4;
-    const int nsh = (kq >> 1) * 4;  // high nibbles for weights 16 .. 31
-    const uint8_t * W = j.W[mat];
-    const uint8_t * wrow[2];
-    const int8_t * xcol[2];
-    const float * xd[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int64_t r = min(r0 + 16 * t + r16, j.N - 1);
-        const int64_t c = min(c0 + 16 * t + r16, j.M - 1);
-        wrow[t] = W + r * j.w_row_bytes;
-        xcol[t] = j.aq.qs + c * j.K;
-        xd[t] = j.aq.d + c * nb;
-    }
-    // rows of this lane's accumulator elements (t, e): r0 + 16 t + 4 kq + e
-    const uint8_t * drow[2][4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) drow[t][e] = W + min(r0 + 16 * t + 4 * kq + e, j.N - 1) * j.w_row_bytes;
-    float acc[2][2][4];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[a][b][e] = 0.0f;
-    long av[2], bv[2], an[2], bn[2];
-    float dwv[2][4], dxv[2], dwn[2][4], dxn[2];
-    auto load = [&](int b, long (&fa)[2], long (&fb)[2], float (&fw)[2][4], float (&fx)[2]) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const uint8_t * blk = wrow[t] + (int64_t)b * 18;
-            const uint16_t * q = (const uint16_t *)(blk + 2 + 8 * (kq & 1));
-            const uint32_t q0 = (uint32_t)q[0] | ((uint32_t)q[1] << 16), q1 = (uint32_t)q[2] | ((uint32_t)q[3] << 16);
-            const uint32_t lo = q40_s8((q0 >> nsh) & 0x0F0F0F0Fu);
-            const uint32_t hi = q40_s8((q1 >> nsh) & 0x0F0F0F0Fu);
-            fa[t] = (long)(((uint64_t)hi << 32) | lo);
-            fb[t] = *(const long *)(xcol[t] + (int64_t)b * QK8_0 + 8 * kq);
-            fx[t] = xd[t][b];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) fw[t][e] = dev_fp16_to_fp32(*(const uint16_t *)(drow[t][e] + (int64_t)b * 18));
-        }
-    };
-    load(0, av, bv, dwv, dxv);
-    for (int b = 0; b < nb; ++b) {
-        if (b + 1 < nb) load(b + 1, an, bn, dwn, dxn);
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj) {
-                const i32x4_t z = {0, 0, 0, 0};
-                const i32x4_t s = __builtin_amdgcn_mfma_i32_16x16x32_i8(av[ti], bv[tj], z, 0, 0, 0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[ti][tj][e] = __fadd_rn(acc[ti][tj][e], q40_term(s[e], dwv[ti][e], dxv[tj]));
+                for (int e = 0; e < 4; ++e) acc[ti][tj][e] = __fadd_rn(acc[ti][tj][e], F::term(s[e], dwv[ti][e], dxv[tj]));
             }
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -3568,27 +3044,39 @@ __global__ __launch_bounds__(256) void k_gemm_q4_0(GemvJob j) {
 // 64-row x TC-column output tile; the K dimension runs in stages of 8 blocks (256 elements), each
 // stage's operands fetched into registers while the previous stage computes, then stored to the other
 // of two LDS buffers:
-//   A: the 64 rows' native 272-B stage spans, row-major (17 x 16 B per row; row stride 68 dwords puts
-//      the 16 rows an MFMA reads on distinct banks), read as 3 dwords + funnel shift (quants start
-//      2 B into a block) and the block's fp16 d as one u16;
+//   A: the 64 rows' native stage spans of SPAN = 8 * F::BYTES = 272 / 176 / 144 B, row-major (17 / 11 / 9 chunks of
+//      16 B per row; row stride 68 dwords puts the 16 rows an MFMA reads on distinct banks, 44 and 36 dwords put
+//      them 4 banks apart), read as 3 dwords + funnel shift (b32_octet_lds: the eight payload bytes start 0 or 2 B
+//      off a dword; the third dword of the last row's last Q4_0 block lies in the slack and is shifted out), for
+//      Q5_0 the qh byte and always the block's fp16 d as single reads;
 //   B: the TC columns' 256 int8, 16-B chunks XOR-swizzled by column (chunk q of column c at slot
 //      q ^ (c & 15)) so the 16 columns of an MFMA read different banks;
 //   dx: the TC columns' 8 block scales.
 // Per block and 16 x 16 tile one v_mfma_i32_16x16x32_i8 gives the exact block dots; each lane folds
-// its four outputs' terms into f32 in block order with ggml's roundings, as k_gemm_q8_0: bit-identical.
-template <int TC>
-struct Q8s {
-    static constexpr int A_BYTES = 20 * 1024;  // 64 rows x 272 B (1088 chunks) as 20 x 64 uniform 16-B chunks
+// its four outputs' terms into f32 in block order with ggml's roundings, as k_gemm_b32: bit-identical.
+// The A stage's 64 * SPAN / 16 = 1088 / 704 / 576 chunks are fetched as A_LOADS = 5 / 3 / 3 uniform loads of 64
+// chunks per wave; the slots past the last chunk re-read it into slack.  For Q4_0 that is 192 slots, which
+// measured faster on weights from HBM than nine groups split 3 / 2 / 2 / 2 over the waves.
+// LDS: 2 x (A_BYTES + TC / 4 + TC / 32 KB) = 2 x (20 | 12 | 12 + 36) KB at TC = 128.
+template <class F, int TC>
+struct B32s {
+    static constexpr int SPAN = 8 * F::BYTES;                  // a row's bytes per stage
+    static constexpr int ROW_CHUNKS = SPAN / 16;
+    static constexpr int A_CHUNKS = 64 * ROW_CHUNKS;           // 64 rows
+    static constexpr int A_LOADS = (A_CHUNKS + 255) / 256;     // per wave, 4 waves x 64 lanes
+    static constexpr int A_BYTES = A_LOADS * 4096;             // as 4 * A_LOADS x 64 uniform 16-B chunks
     static constexpr int B_BYTES = TC * 256;
     static constexpr int D_BYTES = TC * 32;
     static constexpr int STAGE = A_BYTES + B_BYTES + D_BYTES;
 };
-template <int TC>
-__global__ __launch_bounds__(256) void k_gemm_q8_0s(GemvJob j) {
+template <class F, int TC>
+__global__ __launch_bounds__(256) void k_gemm_b32s(GemvJob j) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    using L = B32s<F, TC>;
     constexpr int NT = TC / 32;  // 16-column tiles per wave
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l16 = lane & 15, kq = lane >> 4;
+    const int nsh = F::nsh(kq);
     const int mat = blockIdx.z;
     const int64_t row0 = (int64_t)blockIdx.x * 64, col0 = (int64_t)blockIdx.y * TC;
     const int64_t rb = j.w_row_bytes, K = j.K;
@@ -3596,21 +3084,22 @@ __global__ __launch_bounds__(256) void k_gemm_q8_0s(GemvJob j) {
     const char * W = (const char *)j.W[mat];
     const char * xq = (const char *)j.aq.qs;
     const char * xdg = (const char *)j.aq.d;
-    // a wave's share of one stage: 5 A chunks, TC / 16 B chunks, <= 1 dx chunk (16 B each), fetched into
+    // a wave's share of one stage: A_LOADS A chunks, TC / 16 B chunks, <= 1 dx chunk (16 B each), fetched into
     // registers while the previous stage computes, then stored to LDS (a lane's chunk of instruction
     // `ins` at slot ins * 64 + lane).  Register staging, not LDS-DMA: the compiler cannot tell a DMA's
     // LDS target from the buffer being read and would wait for the DMA before every LDS read.
     constexpr int NB_ = TC / 16;
-    u32x4 ra[5], rbv[NB_], rd;
+    u32x4 ra[L::A_LOADS], rbv[NB_], rd;
     auto stage_load = [&](int st) __attribute__((always_inline)) {
 #pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            // A: linear chunk n = r * 17 + q (n < 1088; the rest re-read the last chunk into the slack)
-            int n = (wave * 5 + i) * 64 + lane;
-            n = n < 1088 ? n : 1087;
-            const int r = n / 17, q = n - 17 * (n / 17);
+        for (int i = 0; i < L::A_LOADS; ++i) {
+            // A: linear chunk n = r * ROW_CHUNKS + q (n < A_CHUNKS; the rest re-read the last chunk into the slack),
+            // every wave's loads unconditional
+            int n = (wave * L::A_LOADS + i) * 64 + lane;
+            n = n < L::A_CHUNKS ? n : L::A_CHUNKS - 1;
+            const int r = n / L::ROW_CHUNKS, q = n - L::ROW_CHUNKS * r;
             const int64_t row = row0 + r < j.N ? row0 + r : j.N - 1;
-            ra[i] = *gptr((const u32x4 *)(W + row * rb + (int64_t)st * 272 + 16 * q));
+            ra[i] = *gptr((const u32x4 *)(W + row * rb + (int64_t)st * L::SPAN + 16 * q));
         }
 #pragma unroll
         for (int i = 0; i < NB_; ++i) {
@@ -3627,13 +3116,13 @@ __global__ __launch_bounds__(256) void k_gemm_q8_0s(GemvJob j) {
         }
     };
     auto stage_store = [&](int buf) __attribute__((always_inline)) {
-        char * base = smem + buf * Q8s<TC>::STAGE;
+        char * base = smem + buf * L::STAGE;
 #pragma unroll
-        for (int i = 0; i < 5; ++i) *(u32x4 *)(base + (wave * 5 + i) * 1024 + 16 * lane) = ra[i];
-        char * bb = base + Q8s<TC>::A_BYTES;
+        for (int i = 0; i < L::A_LOADS; ++i) *(u32x4 *)(base + (wave * L::A_LOADS + i) * 1024 + 16 * lane) = ra[i];
+        char * bb = base + L::A_BYTES;
 #pragma unroll
         for (int i = 0; i < NB_; ++i) *(u32x4 *)(bb + (wave * NB_ + i) * 1024 + 16 * lane) = rbv[i];
-        if (wave < TC / 32) *(u32x4 *)(bb + Q8s<TC>::B_BYTES + wave * 1024 + 16 * lane) = rd;
+        if (wave < TC / 32) *(u32x4 *)(bb + L::B_BYTES + wave * 1024 + 16 * lane) = rd;
     };
     const int wr = (wave & 1) * 32, wc = (wave >> 1) * (TC / 2);
     float acc[2][NT][4];
@@ -3648,9 +3137,9 @@ __global__ __launch_bounds__(256) void k_gemm_q8_0s(GemvJob j) {
     __syncthreads();
     for (int st = 0; st < nst; ++st) {
         stage_load(st + 1 < nst ? st + 1 : st);  // unconditional (clamped): lands during this stage's MFMAs
-        const char * base = smem + (st & 1) * Q8s<TC>::STAGE;
-        const char * bb = base + Q8s<TC>::A_BYTES;
-        const float * db = (const float *)(bb + Q8s<TC>::B_BYTES);
+        const char * base = smem + (st & 1) * L::STAGE;
+        const char * bb = base + L::A_BYTES;
+        const float * db = (const float *)(bb + L::B_BYTES);
         // all of a block's MFMAs are issued before any result is folded, so they pipeline instead of
         // each waiting out the previous one's latency
 #pragma unroll 2
@@ -3659,15 +3148,10 @@ __global__ __launch_bounds__(256) void k_gemm_q8_0s(GemvJob j) {
             float dw[2][4], dx[NT];
 #pragma unroll
             for (int ti = 0; ti < 2; ++ti) {
-                const int off = (wr + 16 * ti + l16) * 272 + b * 34 + 2 + 8 * kq;
-                const uint32_t * p = (const uint32_t *)(base + (off & ~3));
-                const uint32_t d0 = p[0], d1 = p[1], d2 = p[2];
-                const uint32_t sh = (off & 3) * 8;
-                const uint32_t lo = __builtin_amdgcn_alignbit(d1, d0, sh), hi = __builtin_amdgcn_alignbit(d2, d1, sh);
-                av[ti] = (long)(((uint64_t)hi << 32) | lo);
+                av[ti] = b32_octet_lds<F>(base, (wr + 16 * ti + l16) * L::SPAN + b * F::BYTES, kq, nsh);
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    dw[ti][e] = dev_fp16_to_fp32(*(const uint16_t *)(base + (wr + 16 * ti + 4 * kq + e) * 272 + b * 34));
+                    dw[ti][e] = dev_fp16_to_fp32(*(const uint16_t *)(base + (wr + 16 * ti + 4 * kq + e) * L::SPAN + b * F::BYTES));
             }
 #pragma unroll
             for (int tj = 0; tj < NT; ++tj) {
@@ -3690,8 +3174,7 @@ __global__ __launch_bounds__(256) void k_gemm_q8_0s(GemvJob j) {
 #pragma unroll
                 for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        acc[ti][tj][e] = __fadd_rn(acc[ti][tj][e], __fmul_rn((float)sv[ti][tj][e], __fmul_rn(dw[ti][e], dx[tj])));
+                    for (int e = 0; e < 4; ++e) acc[ti][tj][e] = __fadd_rn(acc[ti][tj][e], F::term(sv[ti][tj][e], dw[ti][e], dx[tj]));
         }
         // every wave is done with the other buffer (stage st - 1) since the last barrier
         if (st + 1 < nst) stage_store((st + 1) & 1);
@@ -3711,455 +3194,89 @@ __global__ __launch_bounds__(256) void k_gemm_q8_0s(GemvJob j) {
         }
 }
 
-static bool gemm_q8s_ok(const tts_hip_backend * be, const GemvJob & j) {
-    if (be->gemm_q8_staged <= 0 || j.K % QK_K || j.w_row_bytes % 16 || ((uintptr_t)j.aq.qs & 15) || ((uintptr_t)j.aq.d & 15)) return false;
-    for (int m = 0; m < j.nmat; ++m)
-        if ((uintptr_t)j.W[m] & 15) return false;
-    return true;
+// The one wtype -> trait dispatch: f(F{}) for the 32-weight format of `wtype` (wtype_q80_act(wtype) holds)
+template <class Fn>
+static void b32_dispatch(int wtype, Fn && f) {
+    switch (wtype) {
+        case TTS_TYPE_Q8_0: f(BlkQ8_0{}); break;
+        case TTS_TYPE_Q5_0: f(BlkQ5_0{}); break;
+        default: f(BlkQ4_0{}); break;
+    }
 }
 
-static void launch_gemm_q8_0(tts_hip_backend * be, const GemvJob & j) {
-    if (gemm_q8s_ok(be, j)) {
+// the many-column GEMM: staged where K % 256 == 0 and rows and activation copy are 16-B aligned, each format on its own options
+template <class F>
+static void launch_gemm_b32(tts_hip_backend * be, const GemvJob & j) {
+    const int opt = be->b32[b32_index(F::TYPE)].staged;
+    bool staged = opt > 0 && j.K % QK_K == 0 && j.w_row_bytes % 16 == 0 && !((uintptr_t)j.aq.qs & 15) && !((uintptr_t)j.aq.d & 15);
+    for (int m = 0; m < j.nmat; ++m) staged = staged && !((uintptr_t)j.W[m] & 15);
+    if (staged) {
         static std::atomic<uint32_t> attr_done[2];
-        if (be->gemm_q8_staged == 1) {
-            set_lds_attr_once(attr_done[0], be->device, (const void *)k_gemm_q8_0s<64>);
+        if (opt == 1) {
+            set_lds_attr_once(attr_done[0], be->device, (const void *)k_gemm_b32s<F, 64>);
             const dim3 grid((unsigned)((j.N + 63) / 64), (unsigned)((j.M + 63) / 64), (unsigned)j.nmat);
-            hipLaunchKernelGGL(k_gemm_q8_0s<64>, grid, dim3(256), 2 * Q8s<64>::STAGE, be->stream, j);
+            hipLaunchKernelGGL((k_gemm_b32s<F, 64>), grid, dim3(256), (2 * B32s<F, 64>::STAGE), be->stream, j);
         } else {
-            set_lds_attr_once(attr_done[1], be->device, (const void *)k_gemm_q8_0s<128>);
+            set_lds_attr_once(attr_done[1], be->device, (const void *)k_gemm_b32s<F, 128>);
             const dim3 grid((unsigned)((j.N + 63) / 64), (unsigned)((j.M + 127) / 128), (unsigned)j.nmat);
-            hipLaunchKernelGGL(k_gemm_q8_0s<128>, grid, dim3(256), 2 * Q8s<128>::STAGE, be->stream, j);
+            hipLaunchKernelGGL((k_gemm_b32s<F, 128>), grid, dim3(256), (2 * B32s<F, 128>::STAGE), be->stream, j);
         }
         return;
     }
     const dim3 grid((unsigned)((j.N + 63) / 64), (unsigned)((j.M + 63) / 64), (unsigned)j.nmat);
-    hipLaunchKernelGGL(k_gemm_q8_0, grid, dim3(256), 0, be->stream, j);
+    hipLaunchKernelGGL(k_gemm_b32<F>, grid, dim3(256), 0, be->stream, j);
 }
 
-// slab-form Q8_0 GEMV: whole 16-B aligned rows (K % 256 == 0), activation quantized by the prologue or
+// slab-form GEMV: whole 16-B aligned rows (K % 256 == 0), activation quantized by the prologue or
 // by the quantize launch (Q8_0 blocks at j.aq)
-static bool q80s_ok(const tts_hip_backend * be, const GemvJob & j) {
-    if (!be->gemv_q80_slab || j.K % QK_K || j.hetero || j.dbg) return false;
+template <class F>
+static bool b32s_ok(const tts_hip_backend * be, const GemvJob & j) {
+    if (!be->b32[b32_index(F::TYPE)].slab || j.K % QK_K || j.hetero || j.dbg) return false;
     if (!j.pro && (j.aq.vtype != TTS_TYPE_Q8_0 || ((uintptr_t)j.aq.qs & 15) || ((uintptr_t)j.aq.d & 15))) return false;
     for (int m = 0; m < j.nmat; ++m)
         if ((uintptr_t)j.W[m] & 15) return false;
-    return q80s_lds(8, j.K, 1) <= 160 * 1024;
+    return b32s_lds<F>(8, j.K, 1) <= 160 * 1024;
 }
-template <int MC>
-static void launch_q80s(tts_hip_backend * be, const GemvJob & j) {
+template <class F, int MC>
+static void launch_b32s(tts_hip_backend * be, const GemvJob & j) {
     // rows per workgroup: the largest of 32 / 16 / 8 / 4 / 2 / 1 that still gives every CU a workgroup
-    // and fits LDS (option TTS_HIP_OPT_GEMV_Q80_RW overrides)
-    int RW = be->gemv_q80_rw > 0 ? be->gemv_q80_rw : 32;
-    if (be->gemv_q80_rw <= 0)
+    // and fits LDS (options TTS_HIP_OPT_GEMV_Q80_RW / _Q50_RW / _Q40_RW override)
+    const int rw = be->b32[b32_index(F::TYPE)].rw;
+    int RW = rw > 0 ? rw : 32;
+    if (rw <= 0)
         while (RW > 1 && (j.N + RW - 1) / RW * j.nmat < be->cus) RW /= 2;
-    while (RW > 1 && q80s_lds(MC, j.K, RW) > (be->gemv_q80_rw > 0 ? 160 : 80) * 1024) RW /= 2;  // auto: 2+ workgroups per CU
-    const size_t lds = q80s_lds(MC, j.K, RW);
+    while (RW > 1 && b32s_lds<F>(MC, j.K, RW) > (rw > 0 ? 160 : 80) * 1024) RW /= 2;  // auto: 2+ workgroups per CU
+    const size_t lds = b32s_lds<F>(MC, j.K, RW);
     const dim3 grid((unsigned)((j.N + RW - 1) / RW), (unsigned)j.nmat);
     static std::atomic<uint32_t> attr_done[3];
-    // profiled: in-packet events (the Dia leg's roofline; launch_gemv_job leaves Q8_0 slab jobs to this)
+    // profiled: in-packet events (the Dia leg's roofline; launch_gemv_job leaves slab jobs to this)
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (be->profile_gemv) profile_pair(be, e0, e1);
     if (j.pro == PRO_LN) {
-        set_lds_attr_once(attr_done[2], be->device, (const void *)k_gemv_q8_0s<MC, PRO_LN>);
-        hipExtLaunchKernelGGL((k_gemv_q8_0s<MC, PRO_LN>), grid, dim3(256), (uint32_t)lds, be->stream, e0, e1, 0u, j, RW);
+        set_lds_attr_once(attr_done[2], be->device, (const void *)k_gemv_b32s<F, MC, PRO_LN>);
+        hipExtLaunchKernelGGL((k_gemv_b32s<F, MC, PRO_LN>), grid, dim3(256), (uint32_t)lds, be->stream, e0, e1, 0u, j, RW);
     } else if (j.pro == PRO_QUANT) {
-        set_lds_attr_once(attr_done[1], be->device, (const void *)k_gemv_q8_0s<MC, PRO_QUANT>);
-        hipExtLaunchKernelGGL((k_gemv_q8_0s<MC, PRO_QUANT>), grid, dim3(256), (uint32_t)lds, be->stream, e0, e1, 0u, j, RW);
+        set_lds_attr_once(attr_done[1], be->device, (const void *)k_gemv_b32s<F, MC, PRO_QUANT>);
+        hipExtLaunchKernelGGL((k_gemv_b32s<F, MC, PRO_QUANT>), grid, dim3(256), (uint32_t)lds, be->stream, e0, e1, 0u, j, RW);
     } else {
-        set_lds_attr_once(attr_done[0], be->device, (const void *)k_gemv_q8_0s<MC>);
-        hipExtLaunchKernelGGL(k_gemv_q8_0s<MC>, grid, dim3(256), (uint32_t)lds, be->stream, e0, e1, 0u, j, RW);
+        set_lds_attr_once(attr_done[0], be->device, (const void *)k_gemv_b32s<F, MC>);
+        hipExtLaunchKernelGGL((k_gemv_b32s<F, MC>), grid, dim3(256), (uint32_t)lds, be->stream, e0, e1, 0u, j, RW);
     }
-    if (be->profile_gemv) profile_push(be, e0, e1, gemv_bytes(j), TTS_TYPE_Q8_0);
+    if (be->profile_gemv) profile_push(be, e0, e1, gemv_bytes(j), F::TYPE);
 }
-
-// The staged Q5_0 GEMM (K % 256 == 0, 16-B aligned weight rows and activation copy): k_gemm_q8_0s with
-// the A operand unpacked as in k_gemm_q5_0.  A stage is 8 blocks: the 64 rows' native 176-B spans,
-// row-major (704 16-B chunks = 11 per row, fetched as 3 x 64 per wave; row stride 44 dwords puts the 16
-// rows an MFMA reads 4 banks apart, and a lane reads 3 dwords); a lane's eight qs bytes are two
-// funnel-shifted dwords (they start 2 B off a dword), its qh byte and the rows' fp16 d single reads.
-// B and dx as Q8s.  LDS: 2 x (12 + TC / 4 + TC / 32) KB = 96 KB at TC = 128.
-template <int TC>
-struct Q5s {
-    static constexpr int A_CHUNKS = 64 * 11;   // 64 rows x 176 B
-    static constexpr int A_BYTES = 12 * 1024;  // as 12 x 64 uniform 16-B chunks (the last 64 are slack)
-    static constexpr int B_BYTES = TC * 256;
-    static constexpr int D_BYTES = TC * 32;
-    static constexpr int STAGE = A_BYTES + B_BYTES + D_BYTES;
-};
-template <int TC>
-__global__ __launch_bounds__(256) void k_gemm_q5_0s(GemvJob j) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NT = TC / 32;  // 16-column tiles per wave
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int l16 = lane & 15, kq = lane >> 4;
-    const int nsh = (kq >> 1) * 4;  // high nibbles for weights 16 .. 31
-    const int mat = blockIdx.z;
-    const int64_t row0 = (int64_t)blockIdx.x * 64, col0 = (int64_t)blockIdx.y * TC;
-    const int64_t rb = j.w_row_bytes, K = j.K;
-    const int nb = (int)(K / QK5_0), nst = nb / 8;
-    const char * W = (const char *)j.W[mat];
-    const char * xq = (const char *)j.aq.qs;
-    const char * xdg = (const char *)j.aq.d;
-    // a wave's share of one stage: 3 A chunks, TC / 16 B chunks, <= 1 dx chunk, through registers (Q8s)
-    constexpr int NB_ = TC / 16;
-    u32x4 ra[3], rbv[NB_], rd;
-    auto stage_load = [&](int st) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            // A: linear chunk n = r * 11 + q (n < 704; the rest re-read the last chunk into the slack)
-            int n = (wave * 3 + i) * 64 + lane;
-            n = n < Q5s<TC>::A_CHUNKS ? n : Q5s<TC>::A_CHUNKS - 1;
-            const int r = n / 11, q = n - 11 * r;
-            const int64_t row = row0 + r < j.N ? row0 + r : j.N - 1;
-            ra[i] = *gptr((const u32x4 *)(W + row * rb + (int64_t)st * 176 + 16 * q));
-        }
-#pragma unroll
-        for (int i = 0; i < NB_; ++i) {
-            // B: slot idx = c * 16 + q' holds chunk q = q' ^ (c & 15) of column c
-            const int idx = (wave * NB_ + i) * 64 + lane, c = idx >> 4, q = (idx & 15) ^ (c & 15);
-            const int64_t col = col0 + c < j.M ? col0 + c : j.M - 1;
-            rbv[i] = *gptr((const u32x4 *)(xq + col * K + (int64_t)st * 256 + 16 * q));
-        }
-        {
-            // dx: column c's 8 scales as chunks 2c, 2c + 1 (waves 0 .. TC/32 - 1)
-            const int idx = (wave < TC / 32 ? wave : 0) * 64 + lane, c = idx >> 1, h = idx & 1;
-            const int64_t col = col0 + c < j.M ? col0 + c : j.M - 1;
-            rd = *gptr((const u32x4 *)(xdg + col * (int64_t)nb * 4 + (int64_t)st * 32 + 16 * h));
-        }
-    };
-    auto stage_store = [&](int buf) __attribute__((always_inline)) {
-        char * base = smem + buf * Q5s<TC>::STAGE;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) *(u32x4 *)(base + (wave * 3 + i) * 1024 + 16 * lane) = ra[i];
-        char * bb = base + Q5s<TC>::A_BYTES;
-#pragma unroll
-        for (int i = 0; i < NB_; ++i) *(u32x4 *)(bb + (wave * NB_ + i) * 1024 + 16 * lane) = rbv[i];
-        if (wave < TC / 32) *(u32x4 *)(bb + Q5s<TC>::B_BYTES + wave * 1024 + 16 * lane) = rd;
-    };
-    const int wr = (wave & 1) * 32, wc = (wave >> 1) * (TC / 2);
-    float acc[2][NT][4];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < NT; ++b)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[a][b][e] = 0.0f;
-    stage_load(0);
-    stage_store(0);
-    __syncthreads();
-    for (int st = 0; st < nst; ++st) {
-        stage_load(st + 1 < nst ? st + 1 : st);  // unconditional (clamped): lands during this stage's MFMAs
-        const char * base = smem + (st & 1) * Q5s<TC>::STAGE;
-        const char * bb = base + Q5s<TC>::A_BYTES;
-        const float * db = (const float *)(bb + Q5s<TC>::B_BYTES);
-#pragma unroll 2
-        for (int b = 0; b < 8; ++b) {
-            long av[2], bv[NT];
-            float dw[2][4], dx[NT];
-#pragma unroll
-            for (int ti = 0; ti < 2; ++ti) {
-                const char * blk = base + (wr + 16 * ti + l16) * 176 + b * 22;
-                const int off = (wr + 16 * ti + l16) * 176 + b * 22 + 6 + 8 * (kq & 1);
-                const uint32_t * p = (const uint32_t *)(base + (off & ~3));
-                const uint32_t d0 = p[0], d1 = p[1], d2 = p[2];
-                const uint32_t sh = (off & 3) * 8;
-                const uint32_t q0 = __builtin_amdgcn_alignbit(d1, d0, sh), q1 = __builtin_amdgcn_alignbit(d2, d1, sh);
-                const uint32_t nqh = ~(uint32_t)*(const uint8_t *)(blk + 2 + kq);
-                const uint32_t lo = ((q0 >> nsh) & 0x0F0F0F0Fu) | q50_himask(nqh, 0);
-                const uint32_t hi = ((q1 >> nsh) & 0x0F0F0F0Fu) | q50_himask(nqh, 4);
-                av[ti] = (long)(((uint64_t)hi << 32) | lo);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    dw[ti][e] = dev_fp16_to_fp32(*(const uint16_t *)(base + (wr + 16 * ti + 4 * kq + e) * 176 + b * 22));
-            }
-#pragma unroll
-            for (int tj = 0; tj < NT; ++tj) {
-                const int c = wc + 16 * tj + l16;
-                const int q = 2 * b + (kq >> 1);
-                bv[tj] = *(const long *)(bb + (c * 16 + (q ^ (c & 15))) * 16 + 8 * (kq & 1));
-                dx[tj] = db[c * 8 + b];
-            }
-            i32x4_t sv[2][NT];
-#pragma unroll
-            for (int tj = 0; tj < NT; ++tj)
-#pragma unroll
-                for (int ti = 0; ti < 2; ++ti) {
-                    const i32x4_t z = {0, 0, 0, 0};
-                    sv[ti][tj] = __builtin_amdgcn_mfma_i32_16x16x32_i8(av[ti], bv[tj], z, 0, 0, 0);
-                }
-            __builtin_amdgcn_sched_barrier(0);  // keep the scheduler from re-serializing them into one accumulator
-#pragma unroll
-            for (int tj = 0; tj < NT; ++tj)
-#pragma unroll
-                for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        acc[ti][tj][e] = __fadd_rn(acc[ti][tj][e], __fmul_rn((float)sv[ti][tj][e], __fmul_rn(dw[ti][e], dx[tj])));
-        }
-        // every wave is done with the other buffer (stage st - 1) since the last barrier
-        if (st + 1 < nst) stage_store((st + 1) & 1);
-        __syncthreads();
-    }
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < NT; ++tj) {
-            const int64_t col = col0 + wc + 16 * tj + l16;
-            if (col >= j.M) continue;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int64_t row = row0 + wr + 16 * ti + 4 * kq + e;
-                if (row < j.N) gemv_store<1>(j, mat, row, (int)col, acc[ti][tj][e]);
-            }
-        }
-}
-
-// Q5_0: the many-column GEMM and the slab GEMV beside the Q8_0 ones (same activation, same conditions)
-static void launch_gemm_q5_0(tts_hip_backend * be, const GemvJob & j) {
-    bool staged = be->gemm_q5_staged > 0 && j.K % QK_K == 0 && j.w_row_bytes % 16 == 0 && !((uintptr_t)j.aq.qs & 15) && !((uintptr_t)j.aq.d & 15);
-    for (int m = 0; m < j.nmat; ++m) staged = staged && !((uintptr_t)j.W[m] & 15);
-    if (staged) {
-        static std::atomic<uint32_t> attr_done[2];
-        if (be->gemm_q5_staged == 1) {
-            set_lds_attr_once(attr_done[0], be->device, (const void *)k_gemm_q5_0s<64>);
-            const dim3 grid((unsigned)((j.N + 63) / 64), (unsigned)((j.M + 63) / 64), (unsigned)j.nmat);
-            hipLaunchKernelGGL(k_gemm_q5_0s<64>, grid, dim3(256), 2 * Q5s<64>::STAGE, be->stream, j);
-        } else {
-            set_lds_attr_once(attr_done[1], be->device, (const void *)k_gemm_q5_0s<128>);
-            const dim3 grid((unsigned)((j.N + 63) / 64), (unsigned)((j.M + 127) / 128), (unsigned)j.nmat);
-            hipLaunchKernelGGL(k_gemm_q5_0s<128>, grid, dim3(256), 2 * Q5s<128>::STAGE, be->stream, j);
-        }
+// <= 8 columns: the slab kernel where it applies, else the general one
+template <class F, int MC>
+static void launch_b32(tts_hip_backend * be, const GemvJob & j) {
+    if (b32s_ok<F>(be, j)) {
+        launch_b32s<F, MC>(be, j);
         return;
     }
-    const dim3 grid((unsigned)((j.N + 63) / 64), (unsigned)((j.M + 63) / 64), (unsigned)j.nmat);
-    hipLaunchKernelGGL(k_gemm_q5_0, grid, dim3(256), 0, be->stream, j);
-}
-
-static bool q50s_ok(const tts_hip_backend * be, const GemvJob & j) {
-    if (!be->gemv_q50_slab || j.K % QK_K || j.hetero || j.dbg) return false;
-    if (!j.pro && (j.aq.vtype != TTS_TYPE_Q8_0 || ((uintptr_t)j.aq.qs & 15) || ((uintptr_t)j.aq.d & 15))) return false;
-    for (int m = 0; m < j.nmat; ++m)
-        if ((uintptr_t)j.W[m] & 15) return false;
-    return q50s_lds(8, j.K, 1) <= 160 * 1024;
-}
-template <int MC>
-static void launch_q50s(tts_hip_backend * be, const GemvJob & j) {
-    // rows per workgroup as launch_q80s chooses them (option TTS_HIP_OPT_GEMV_Q50_RW overrides)
-    int RW = be->gemv_q50_rw > 0 ? be->gemv_q50_rw : 32;
-    if (be->gemv_q50_rw <= 0)
-        while (RW > 1 && (j.N + RW - 1) / RW * j.nmat < be->cus) RW /= 2;
-    while (RW > 1 && q50s_lds(MC, j.K, RW) > (be->gemv_q50_rw > 0 ? 160 : 80) * 1024) RW /= 2;  // auto: 2+ workgroups per CU
-    const size_t lds = q50s_lds(MC, j.K, RW);
+    const int RW = b32_rw(MC, j.K);
+    const size_t lds = b32_lds(MC, j.K, RW, j.pro);
     const dim3 grid((unsigned)((j.N + RW - 1) / RW), (unsigned)j.nmat);
-    static std::atomic<uint32_t> attr_done[3];
-    hipEvent_t e0 = nullptr, e1 = nullptr;  // profiled: in-packet events, as the Q8_0 slab
-    if (be->profile_gemv) profile_pair(be, e0, e1);
-    if (j.pro == PRO_LN) {
-        set_lds_attr_once(attr_done[2], be->device, (const void *)k_gemv_q5_0s<MC, PRO_LN>);
-        hipExtLaunchKernelGGL((k_gemv_q5_0s<MC, PRO_LN>), grid, dim3(256), (uint32_t)lds, be->stream, e0, e1, 0u, j, RW);
-    } else if (j.pro == PRO_QUANT) {
-        set_lds_attr_once(attr_done[1], be->device, (const void *)k_gemv_q5_0s<MC, PRO_QUANT>);
-        hipExtLaunchKernelGGL((k_gemv_q5_0s<MC, PRO_QUANT>), grid, dim3(256), (uint32_t)lds, be->stream, e0, e1, 0u, j, RW);
-    } else {
-        set_lds_attr_once(attr_done[0], be->device, (const void *)k_gemv_q5_0s<MC>);
-        hipExtLaunchKernelGGL(k_gemv_q5_0s<MC>, grid, dim3(256), (uint32_t)lds, be->stream, e0, e1, 0u, j, RW);
-    }
-    if (be->profile_gemv) profile_push(be, e0, e1, gemv_bytes(j), TTS_TYPE_Q5_0);
-}
-
-// The staged Q4_0 GEMM (K % 256 == 0, 16-B aligned weight rows and activation copy): k_gemm_q5_0s with the
-// A operand unpacked as in k_gemm_q4_0.  A stage is 8 blocks: the 64 rows' native 144-B spans, row-major
-// (576 16-B chunks = 9 per row, fetched as 3 x 64 per wave: the 192 slots past 576 re-read the last chunk into
-// slack, which measured faster on weights from HBM than nine groups split 3 / 2 / 2 / 2 over the waves, DESIGN
-// 7g; row stride 36 dwords puts the 16 rows an MFMA reads 4 banks apart, and a lane reads 3 dwords); a lane's
-// eight qs bytes are two funnel-shifted dwords (they start 0 or 2 B off a dword), the rows' fp16 d single reads.
-// The third dword of the last row's last block lies in the slack and is shifted out.  B and dx as Q8s.
-// LDS: 2 x (12 + TC / 4 + TC / 32) KB = 96 KB at TC = 128, 60 KB at TC = 64.
-template <int TC>
-struct Q4s {
-    static constexpr int A_CHUNKS = 64 * 9;    // 64 rows x 144 B
-    static constexpr int A_BYTES = 12 * 1024;  // as 12 x 64 uniform 16-B chunks, three per wave (the last 3 x 64 are slack)
-    static constexpr int B_BYTES = TC * 256;
-    static constexpr int D_BYTES = TC * 32;
-    static constexpr int STAGE = A_BYTES + B_BYTES + D_BYTES;
-};
-template <int TC>
-__global__ __launch_bounds__(256) void k_gemm_q4_0s(GemvJob j) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NT = TC / 32;  // 16-column tiles per wave
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int l16 = lane & 15, kq = lane >> 4;
-    const int nsh = (kq >> 1) * 4;  // high nibbles for weights 16 .. 31
-    const int mat = blockIdx.z;
-    const int64_t row0 = (int64_t)blockIdx.x * 64, col0 = (int64_t)blockIdx.y * TC;
-    const int64_t rb = j.w_row_bytes, K = j.K;
-    const int nb = (int)(K / QK4_0), nst = nb / 8;
-    const char * W = (const char *)j.W[mat];
-    const char * xq = (const char *)j.aq.qs;
-    const char * xdg = (const char *)j.aq.d;
-    // a wave's share of one stage: 3 A chunks, TC / 16 B chunks, <= 1 dx chunk, through registers (Q8s)
-    constexpr int NB_ = TC / 16;
-    u32x4 ra[3], rbv[NB_], rd;
-    auto stage_load = [&](int st) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            // A: linear chunk n = r * 9 + q (n < 576; the rest re-read the last chunk into the slack), every wave
-            // three unconditional loads
-            int n = (wave * 3 + i) * 64 + lane;
-            n = n < Q4s<TC>::A_CHUNKS ? n : Q4s<TC>::A_CHUNKS - 1;
-            const int r = n / 9, q = n - 9 * r;
-            const int64_t row = row0 + r < j.N ? row0 + r : j.N - 1;
-            ra[i] = *gptr((const u32x4 *)(W + row * rb + (int64_t)st * 144 + 16 * q));
-        }
-#pragma unroll
-        for (int i = 0; i < NB_; ++i) {
-            // B: slot idx = c * 16 + q' holds chunk q = q' ^ (c & 15) of column c
-            const int idx = (wave * NB_ + i) * 64 + lane, c = idx >> 4, q = (idx & 15) ^ (c & 15);
-            const int64_t col = col0 + c < j.M ? col0 + c : j.M - 1;
-            rbv[i] = *gptr((const u32x4 *)(xq + col * K + (int64_t)st * 256 + 16 * q));
-        }
-        {
-            // dx: column c's 8 scales as chunks 2c, 2c + 1 (waves 0 .. TC/32 - 1)
-            const int idx = (wave < TC / 32 ? wave : 0) * 64 + lane, c = idx >> 1, h = idx & 1;
-            const int64_t col = col0 + c < j.M ? col0 + c : j.M - 1;
-            rd = *gptr((const u32x4 *)(xdg + col * (int64_t)nb * 4 + (int64_t)st * 32 + 16 * h));
-        }
-    };
-    auto stage_store = [&](int buf) __attribute__((always_inline)) {
-        char * base = smem + buf * Q4s<TC>::STAGE;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) *(u32x4 *)(base + (wave * 3 + i) * 1024 + 16 * lane) = ra[i];
-        char * bb = base + Q4s<TC>::A_BYTES;
-#pragma unroll
-        for (int i = 0; i < NB_; ++i) *(u32x4 *)(bb + (wave * NB_ + i) * 1024 + 16 * lane) = rbv[i];
-        if (wave < TC / 32) *(u32x4 *)(bb + Q4s<TC>::B_BYTES + wave * 1024 + 16 * lane) = rd;
-    };
-    const int wr = (wave & 1) * 32, wc = (wave >> 1) * (TC / 2);
-    float acc[2][NT][4];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < NT; ++b)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[a][b][e] = 0.0f;
-    stage_load(0);
-    stage_store(0);
-    __syncthreads();
-    for (int st = 0; st < nst; ++st) {
-        stage_load(st + 1 < nst ? st + 1 : st);  // unconditional (clamped): lands during this stage's MFMAs
-        const char * base = smem + (st & 1) * Q4s<TC>::STAGE;
-        const char * bb = base + Q4s<TC>::A_BYTES;
-        const float * db = (const float *)(bb + Q4s<TC>::B_BYTES);
-#pragma unroll 2
-        for (int b = 0; b < 8; ++b) {
-            long av[2], bv[NT];
-            float dw[2][4], dx[NT];
-#pragma unroll
-            for (int ti = 0; ti < 2; ++ti) {
-                const int off = (wr + 16 * ti + l16) * 144 + b * 18 + 2 + 8 * (kq & 1);
-                const uint32_t * p = (const uint32_t *)(base + (off & ~3));
-                const uint32_t d0 = p[0], d1 = p[1], d2 = p[2];
-                const uint32_t sh = (off & 3) * 8;
-                const uint32_t q0 = __builtin_amdgcn_alignbit(d1, d0, sh), q1 = __builtin_amdgcn_alignbit(d2, d1, sh);
-                const uint32_t lo = q40_s8((q0 >> nsh) & 0x0F0F0F0Fu);
-                const uint32_t hi = q40_s8((q1 >> nsh) & 0x0F0F0F0Fu);
-                av[ti] = (long)(((uint64_t)hi << 32) | lo);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    dw[ti][e] = dev_fp16_to_fp32(*(const uint16_t *)(base + (wr + 16 * ti + 4 * kq + e) * 144 + b * 18));
-            }
-#pragma unroll
-            for (int tj = 0; tj < NT; ++tj) {
-                const int c = wc + 16 * tj + l16;
-                const int q = 2 * b + (kq >> 1);
-                bv[tj] = *(const long *)(bb + (c * 16 + (q ^ (c & 15))) * 16 + 8 * (kq & 1));
-                dx[tj] = db[c * 8 + b];
-            }
-            i32x4_t sv[2][NT];
-#pragma unroll
-            for (int tj = 0; tj < NT; ++tj)
-#pragma unroll
-                for (int ti = 0; ti < 2; ++ti) {
-                    const i32x4_t z = {0, 0, 0, 0};
-                    sv[ti][tj] = __builtin_amdgcn_mfma_i32_16x16x32_i8(av[ti], bv[tj], z, 0, 0, 0);
-                }
-            __builtin_amdgcn_sched_barrier(0);  // keep the scheduler from re-serializing them into one accumulator
-#pragma unroll
-            for (int tj = 0; tj < NT; ++tj)
-#pragma unroll
-                for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[ti][tj][e] = __fadd_rn(acc[ti][tj][e], q40_term(sv[ti][tj][e], dw[ti][e], dx[tj]));
-        }
-        // every wave is done with the other buffer (stage st - 1) since the last barrier
-        if (st + 1 < nst) stage_store((st + 1) & 1);
-        __syncthreads();
-    }
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < NT; ++tj) {
-            const int64_t col = col0 + wc + 16 * tj + l16;
-            if (col >= j.M) continue;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int64_t row = row0 + wr + 16 * ti + 4 * kq + e;
-                if (row < j.N) gemv_store<1>(j, mat, row, (int)col, acc[ti][tj][e]);
-            }
-        }
-}
-
-// Q4_0: the same two beside them, on its own options
-static void launch_gemm_q4_0(tts_hip_backend * be, const GemvJob & j) {
-    bool staged = be->gemm_q4_0_staged > 0 && j.K % QK_K == 0 && j.w_row_bytes % 16 == 0 && !((uintptr_t)j.aq.qs & 15) && !((uintptr_t)j.aq.d & 15);
-    for (int m = 0; m < j.nmat; ++m) staged = staged && !((uintptr_t)j.W[m] & 15);
-    if (staged) {
-        static std::atomic<uint32_t> attr_done[2];
-        if (be->gemm_q4_0_staged == 1) {
-            set_lds_attr_once(attr_done[0], be->device, (const void *)k_gemm_q4_0s<64>);
-            const dim3 grid((unsigned)((j.N + 63) / 64), (unsigned)((j.M + 63) / 64), (unsigned)j.nmat);
-            hipLaunchKernelGGL(k_gemm_q4_0s<64>, grid, dim3(256), 2 * Q4s<64>::STAGE, be->stream, j);
-        } else {
-            set_lds_attr_once(attr_done[1], be->device, (const void *)k_gemm_q4_0s<128>);
-            const dim3 grid((unsigned)((j.N + 63) / 64), (unsigned)((j.M + 127) / 128), (unsigned)j.nmat);
-            hipLaunchKernelGGL(k_gemm_q4_0s<128>, grid, dim3(256), 2 * Q4s<128>::STAGE, be->stream, j);
-        }
-        return;
-    }
-    const dim3 grid((unsigned)((j.N + 63) / 64), (unsigned)((j.M + 63) / 64), (unsigned)j.nmat);
-    hipLaunchKernelGGL(k_gemm_q4_0, grid, dim3(256), 0, be->stream, j);
-}
-
-static bool q40s_ok(const tts_hip_backend * be, const GemvJob & j) {
-    if (!be->gemv_q40_slab || j.K % QK_K || j.hetero || j.dbg) return false;
-    if (!j.pro && (j.aq.vtype != TTS_TYPE_Q8_0 || ((uintptr_t)j.aq.qs & 15) || ((uintptr_t)j.aq.d & 15))) return false;
-    for (int m = 0; m < j.nmat; ++m)
-        if ((uintptr_t)j.W[m] & 15) return false;
-    return q40s_lds(8, j.K, 1) <= 160 * 1024;
-}
-template <int MC>
-static void launch_q40s(tts_hip_backend * be, const GemvJob & j) {
-    // rows per workgroup as launch_q80s chooses them (option TTS_HIP_OPT_GEMV_Q40_RW overrides)
-    int RW = be->gemv_q40_rw > 0 ? be->gemv_q40_rw : 32;
-    if (be->gemv_q40_rw <= 0)
-        while (RW > 1 && (j.N + RW - 1) / RW * j.nmat < be->cus) RW /= 2;
-    while (RW > 1 && q40s_lds(MC, j.K, RW) > (be->gemv_q40_rw > 0 ? 160 : 80) * 1024) RW /= 2;  // auto: 2+ workgroups per CU
-    const size_t lds = q40s_lds(MC, j.K, RW);
-    const dim3 grid((unsigned)((j.N + RW - 1) / RW), (unsigned)j.nmat);
-    static std::atomic<uint32_t> attr_done[3];
-    hipEvent_t e0 = nullptr, e1 = nullptr;  // profiled: in-packet events, as the Q8_0 slab
-    if (be->profile_gemv) profile_pair(be, e0, e1);
-    if (j.pro == PRO_LN) {
-        set_lds_attr_once(attr_done[2], be->device, (const void *)k_gemv_q4_0s<MC, PRO_LN>);
-        hipExtLaunchKernelGGL((k_gemv_q4_0s<MC, PRO_LN>), grid, dim3(256), (uint32_t)lds, be->stream, e0, e1, 0u, j, RW);
-    } else if (j.pro == PRO_QUANT) {
-        set_lds_attr_once(attr_done[1], be->device, (const void *)k_gemv_q4_0s<MC, PRO_QUANT>);
-        hipExtLaunchKernelGGL((k_gemv_q4_0s<MC, PRO_QUANT>), grid, dim3(256), (uint32_t)lds, be->stream, e0, e1, 0u, j, RW);
-    } else {
-        set_lds_attr_once(attr_done[0], be->device, (const void *)k_gemv_q4_0s<MC>);
-        hipExtLaunchKernelGGL(k_gemv_q4_0s<MC>, grid, dim3(256), (uint32_t)lds, be->stream, e0, e1, 0u, j, RW);
-    }
-    if (be->profile_gemv) profile_push(be, e0, e1, gemv_bytes(j), TTS_TYPE_Q4_0);
+    if (j.pro == PRO_LN) hipLaunchKernelGGL((k_gemv_b32<F, MC, PRO_LN>), grid, dim3(256), lds, be->stream, j, RW);
+    else if (j.pro == PRO_QUANT) hipLaunchKernelGGL((k_gemv_b32<F, MC, PRO_QUANT>), grid, dim3(256), lds, be->stream, j, RW);
+    else hipLaunchKernelGGL((k_gemv_b32<F, MC>), grid, dim3(256), lds, be->stream, j, RW);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -4387,45 +3504,11 @@ static void launch_gemv_mc(tts_hip_backend * be, const GemvJob & j) {
     const unsigned nmat = (unsigned)j.nmat;
     switch (j.wtype) {
         case TTS_TYPE_Q4_K: launch_gemv_q4k_mc<MC>(be, j); break;
-        case TTS_TYPE_Q5_0: {
-            if (q50s_ok(be, j)) {
-                launch_q50s<MC>(be, j);
-                break;
-            }
-            int RW = 8;  // the general kernel's LDS layout is k_gemv_q8_0's
-            while (RW > 1 && q80_lds(MC, j.K, RW) > 64 * 1024) RW /= 2;
-            const size_t lds = q80_lds(MC, j.K, RW) + (j.pro ? QK_K + 64 : 0);
-            const unsigned grid = (unsigned)((j.N + RW - 1) / RW);
-            if (j.pro == PRO_LN) hipLaunchKernelGGL((k_gemv_q5_0<MC, PRO_LN>), dim3(grid, nmat), dim3(256), lds, be->stream, j, RW);
-            else if (j.pro == PRO_QUANT) hipLaunchKernelGGL((k_gemv_q5_0<MC, PRO_QUANT>), dim3(grid, nmat), dim3(256), lds, be->stream, j, RW);
-            else hipLaunchKernelGGL(k_gemv_q5_0<MC>, dim3(grid, nmat), dim3(256), lds, be->stream, j, RW);
-        } break;
-        case TTS_TYPE_Q4_0: {
-            if (q40s_ok(be, j)) {
-                launch_q40s<MC>(be, j);
-                break;
-            }
-            int RW = 8;  // the general kernel's LDS layout is k_gemv_q8_0's
-            while (RW > 1 && q80_lds(MC, j.K, RW) > 64 * 1024) RW /= 2;
-            const size_t lds = q80_lds(MC, j.K, RW) + (j.pro ? QK_K + 64 : 0);
-            const unsigned grid = (unsigned)((j.N + RW - 1) / RW);
-            if (j.pro == PRO_LN) hipLaunchKernelGGL((k_gemv_q4_0<MC, PRO_LN>), dim3(grid, nmat), dim3(256), lds, be->stream, j, RW);
-            else if (j.pro == PRO_QUANT) hipLaunchKernelGGL((k_gemv_q4_0<MC, PRO_QUANT>), dim3(grid, nmat), dim3(256), lds, be->stream, j, RW);
-            else hipLaunchKernelGGL(k_gemv_q4_0<MC>, dim3(grid, nmat), dim3(256), lds, be->stream, j, RW);
-        } break;
-        case TTS_TYPE_Q8_0: {
-            if (q80s_ok(be, j)) {
-                launch_q80s<MC>(be, j);
-                break;
-            }
-            int RW = 8;
-            while (RW > 1 && q80_lds(MC, j.K, RW) > 64 * 1024) RW /= 2;
-            const size_t lds = q80_lds(MC, j.K, RW) + (j.pro ? QK_K + 64 : 0);
-            const unsigned grid = (unsigned)((j.N + RW - 1) / RW);
-            if (j.pro == PRO_LN) hipLaunchKernelGGL((k_gemv_q8_0<MC, PRO_LN>), dim3(grid, nmat), dim3(256), lds, be->stream, j, RW);
-            else if (j.pro == PRO_QUANT) hipLaunchKernelGGL((k_gemv_q8_0<MC, PRO_QUANT>), dim3(grid, nmat), dim3(256), lds, be->stream, j, RW);
-            else hipLaunchKernelGGL(k_gemv_q8_0<MC>, dim3(grid, nmat), dim3(256), lds, be->stream, j, RW);
-        } break;
+        case TTS_TYPE_Q8_0:
+        case TTS_TYPE_Q5_0:
+        case TTS_TYPE_Q4_0:
+            b32_dispatch(j.wtype, [&](auto f) { launch_b32<decltype(f), MC>(be, j); });
+            break;
         case TTS_TYPE_F16: {
             const unsigned grid = (unsigned)((j.N + 3) / 4);
             hipLaunchKernelGGL((k_gemv_float<MC, true>), dim3(grid, nmat), dim3(256), 0, be->stream, j);
@@ -4453,9 +3536,9 @@ void launch_profile_spin(tts_hip_backend * be, double us) {
 
 void launch_gemv_job(tts_hip_backend * be, const GemvJob & job) {
     // Q4_K launches and Q8_0 / Q5_0 / Q4_0 slab GEMVs profile themselves (in-packet events); other jobs are timed whole
-    const bool prof = be->profile_gemv && job.wtype != TTS_TYPE_Q4_K && !(job.wtype == TTS_TYPE_Q8_0 && job.M <= 8 && q80s_ok(be, job)) &&
-                      !(job.wtype == TTS_TYPE_Q5_0 && job.M <= 8 && q50s_ok(be, job)) &&
-                      !(job.wtype == TTS_TYPE_Q4_0 && job.M <= 8 && q40s_ok(be, job));
+    bool slab = false;
+    if (wtype_q80_act(job.wtype) && job.M <= 8) b32_dispatch(job.wtype, [&](auto f) { slab = b32s_ok<decltype(f)>(be, job); });
+    const bool prof = be->profile_gemv && job.wtype != TTS_TYPE_Q4_K && !slab;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (prof) {
         profile_pair(be, e0, e1);
@@ -4470,26 +3553,9 @@ void launch_gemv_job(tts_hip_backend * be, const GemvJob & job) {
         }
         return;
     }
-    if (job.wtype == TTS_TYPE_Q8_0 && job.M > 8 && job.aq.vtype == TTS_TYPE_Q8_0 && !job.hetero && be->gemm_q8) {
-        launch_gemm_q8_0(be, job);  // one matrix-core pass instead of a GEMV launch per 8 columns
-        TTS_HIP_CHECK(hipGetLastError());
-        if (prof) {
-            TTS_HIP_CHECK(hipEventRecord(e1, be->stream));
-            profile_push(be, e0, e1, gemv_bytes(job), job.wtype);
-        }
-        return;
-    }
-    if (job.wtype == TTS_TYPE_Q5_0 && job.M > 8 && job.aq.vtype == TTS_TYPE_Q8_0 && !job.hetero && be->gemm_q5) {
-        launch_gemm_q5_0(be, job);  // one matrix-core pass instead of a GEMV launch per 8 columns
-        TTS_HIP_CHECK(hipGetLastError());
-        if (prof) {
-            TTS_HIP_CHECK(hipEventRecord(e1, be->stream));
-            profile_push(be, e0, e1, gemv_bytes(job), job.wtype);
-        }
-        return;
-    }
-    if (job.wtype == TTS_TYPE_Q4_0 && job.M > 8 && job.aq.vtype == TTS_TYPE_Q8_0 && !job.hetero && be->gemm_q4_0) {
-        launch_gemm_q4_0(be, job);  // one matrix-core pass instead of a GEMV launch per 8 columns
+    if (wtype_q80_act(job.wtype) && job.M > 8 && job.aq.vtype == TTS_TYPE_Q8_0 && !job.hetero && be->b32[b32_index(job.wtype)].gemm) {
+        // one matrix-core pass instead of a GEMV launch per 8 columns
+        b32_dispatch(job.wtype, [&](auto f) { launch_gemm_b32<decltype(f)>(be, job); });
         TTS_HIP_CHECK(hipGetLastError());
         if (prof) {
             TTS_HIP_CHECK(hipEventRecord(e1, be->stream));

@@ -426,7 +426,8 @@ int tts_hip_set_option(tts_hip_backend_t backend, int option, int value);
  * memory (only data, ne and nb are read); mask is [n][P] f32 per sequence (mbs floats apart, 0 = shared) or NULL;
  * out is [hd, H, n, B] contiguous, out2 an optional second copy.  koff / voff / moff / pseq (device arrays of B entries,
  * all or none): sequence b's K / V byte offsets from k->data / v->data (the views' nb[3] is then ignored), its mask
- * offset in floats and its key count (1 .. P), as a coalesced step of runners at different KV lengths launches it. */
+ * offset in floats and its key count (1 .. P), as a coalesced step of runners at different KV lengths launches it.
+ * hd is a multiple of 4 up to 256 and P at most 8192 (the planner's limits), else TTS_STATUS_BAD_ARG. */
 int tts_hip_attn_decode(tts_hip_backend_t backend, const tts_tensor * q, const tts_tensor * k, const tts_tensor * v,
                         const float * mask, int64_t mbs, float scale, float * out, float * out2, const int64_t * koff,
                         const int64_t * voff, const int64_t * moff, const int32_t * pseq);

@@ -68,11 +68,17 @@ __global__ __launch_bounds__(ATTN_THREADS) void k_attn_decode(AttnArgs a) {
 
     // ---- phase A: kq[i] = sum_d (f32)(K[d,i] * q[d]), f64 accumulation (ggml_vec_dot_f32) ----
     // G lanes per position, each owning hd/G contiguous dims (4 when hd = 4G).
+    // A lane group is GW lanes wide, G rounded up to a power of two, so the xor butterfly below closes over the
+    // group and no group straddles a wave (hd = 96: G = 24, GW = 32); its lanes past G hold zeros.
     const int G = hd / 4 <= 64 ? hd / 4 : 64;  // hd = 64 -> 16 lanes, 128 -> 32 lanes
+    int GW = 1;
+    while (GW < G) GW <<= 1;
     const int per_lane = hd / G;
-    const int slot = tid % G, grp = tid / G, ngrp = ATTN_THREADS / G;
-    float qv[8];
-    for (int e = 0; e < per_lane && e < 8; ++e) qv[e] = *(const float *)(qbase + (int64_t)(slot * per_lane + e) * a.q.nb[0]);
+    const int slot = tid % GW, grp = tid / GW, ngrp = ATTN_THREADS / GW;
+    const bool live = slot < G;
+    float qv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (live)
+        for (int e = 0; e < per_lane && e < 8; ++e) qv[e] = *(const float *)(qbase + (int64_t)(slot * per_lane + e) * a.q.nb[0]);
     const bool vec4 = a.k.nb[0] == 4 && per_lane == 4 && (a.k.nb[1] % 16) == 0 && (((uintptr_t)kbase) % 16) == 0;
     for (int i0 = 0; i0 < P; i0 += ngrp * ATTN_UK) {
         float4 kvv[ATTN_UK];
@@ -81,7 +87,7 @@ __global__ __launch_bounds__(ATTN_THREADS) void k_attn_decode(AttnArgs a) {
         for (int u = 0; u < ATTN_UK; ++u) {
             const int i = i0 + u * ngrp + grp;
             kvv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (i < P) {
+            if (i < P && live) {
                 const char * kr = kbase + (int64_t)i * a.k.nb[1] + (int64_t)(slot * per_lane) * a.k.nb[0];
                 if (vec4) kvv[u] = *(const float4 *)kr;
                 else {
@@ -98,7 +104,7 @@ __global__ __launch_bounds__(ATTN_THREADS) void k_attn_decode(AttnArgs a) {
             s += (double)__fmul_rn(kvv[u].y, qv[1]);
             s += (double)__fmul_rn(kvv[u].z, qv[2]);
             s += (double)__fmul_rn(kvv[u].w, qv[3]);
-            for (int off = G / 2; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+            for (int off = GW / 2; off >= 1; off >>= 1) s += __shfl_xor(s, off);
             const int i = i0 + u * ngrp + grp;
             if (slot == 0 && i < P) s_p[i] = (float)s;
         }
@@ -1501,7 +1507,7 @@ extern "C" int tts_hip_attn_decode(tts_hip_backend_t be, const tts_tensor * q, c
     if (!be || !q || !k || !v || !out || !q->data || !k->data || !v->data) return TTS_STATUS_BAD_ARG;
     if (q->type != TTS_TYPE_F32 || k->type != TTS_TYPE_F32 || v->type != TTS_TYPE_F32) return TTS_STATUS_BAD_ARG;
     const int64_t hd = q->ne[0], n = q->ne[1], H = q->ne[2], B = q->ne[3], P = k->ne[1];
-    if (hd <= 0 || hd % 4 || n <= 0 || H <= 0 || B <= 0 || P <= 0 || P > tts::ATTN_MAXP) return TTS_STATUS_BAD_ARG;
+    if (hd <= 0 || hd % 4 || hd > 256 || n <= 0 || H <= 0 || B <= 0 || P <= 0 || P > tts::ATTN_MAXP) return TTS_STATUS_BAD_ARG;
     if (k->ne[0] != hd || v->ne[0] != P || v->ne[1] != hd) return TTS_STATUS_BAD_ARG;
     // heads and sequences of K / V divide the query's (GQA, shared cross-attention caches)
     if (k->ne[2] <= 0 || H % k->ne[2] || v->ne[2] <= 0 || H % v->ne[2]) return TTS_STATUS_BAD_ARG;

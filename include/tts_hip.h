@@ -435,9 +435,15 @@ int tts_hip_attn_decode(tts_hip_backend_t backend, const tts_tensor * q, const t
  * carried, [2] steps a member ran alone after waiting, [3] groups refused (no coalesced form / mismatched
  * members), [4] the largest group, [5] host microseconds spent waiting for members, [6] coalesced launches whose
  * members were at different KV lengths, [7] host microseconds in the coalesced steps' execution (grouping,
- * layout, plan, tables, launches), [8] of it in the executor layout, [9] planning, [10] tables (co_prepare + upload).
- * Returns the number written. */
+ * layout, plan, tables, launches), [8] of it in the executor layout, [9] planning, [10] tables (co_prepare + upload),
+ * [11] node runs made once per member inside coalesced steps (0 when every node of the steps had a batched form).
+ * Returns the number written (at most 12; a caller passing a smaller n gets the first n). */
 int tts_hip_coalesce_stats(int device, int64_t * out, int n);
+/* The host check a coalesced step makes for every destination of its batched KV store before the destination
+ * tables are uploaded: an F32 view of shape ne[4] and byte strides nb[4], placed off_bytes into a cache tensor of
+ * cache_bytes, lies inside that tensor on 4-byte boundaries.  Pure arithmetic (no device).  1 = inside, 0 = refused:
+ * the group is then refused and every member runs its own graph. */
+int tts_hip_coalesce_store_ok(int64_t off_bytes, const int64_t * ne, const int64_t * nb, int64_t cache_bytes);
 /* Coalescer rendezvous window (microseconds a step waits for the other active members; default 5000). */
 void tts_hip_coalesce_set_wait(int us);
 /* The step coalescer, process-wide: one-prompt decode steps of several backends on one device rendezvous and run

@@ -632,11 +632,26 @@ extern "C" int tts_hip_coalesce_stats(int device, int64_t * out, int n) {
     tts::Dev & d = tts::g_dev[device];
     std::lock_guard<std::mutex> lk(d.mu);
     const tts_hip_backend * ex = d.exec;
-    const int64_t v[11] = {d.launches, d.member_steps, d.alone, d.refused, d.max_group, d.wait_us, d.ragged, d.exec_ns / 1000,
-                           d.layout_ns / 1000, ex ? ex->cap_plan_ns / 1000 : 0, ex ? ex->co_prep_ns / 1000 : 0};
+    const int64_t v[12] = {d.launches, d.member_steps, d.alone, d.refused, d.max_group, d.wait_us, d.ragged, d.exec_ns / 1000,
+                           d.layout_ns / 1000, ex ? ex->cap_plan_ns / 1000 : 0, ex ? ex->co_prep_ns / 1000 : 0,
+                           ex ? ex->co_node_runs : 0};
     int k = 0;
-    for (; k < n && k < 11; ++k) out[k] = v[k];
+    for (; k < n && k < 12; ++k) out[k] = v[k];
     return k;
+}
+
+// The host check every destination of a coalesced step's batched KV store passes before its offset table is
+// uploaded (co_prepare): an F32 view of ne / nb (bytes) placed off_bytes into a cache tensor of cache_bytes lies
+// inside it, on 4-byte boundaries.  Pure arithmetic, no device: 1 = inside, 0 = refused.
+extern "C" int tts_hip_coalesce_store_ok(int64_t off_bytes, const int64_t * ne, const int64_t * nb, int64_t cache_bytes) {
+    if (!ne || !nb || off_bytes < 0 || (off_bytes & 3) || cache_bytes < 4) return 0;
+    int64_t span = 4;  // the last element's end
+    for (int d = 0; d < 4; ++d) {
+        if (ne[d] < 1 || nb[d] < 0 || (nb[d] & 3)) return 0;
+        if (ne[d] > 1 && nb[d] > (cache_bytes - span) / (ne[d] - 1)) return 0;  // (no overflow)
+        span += (ne[d] - 1) * nb[d];
+    }
+    return off_bytes <= cache_bytes - span ? 1 : 0;
 }
 
 extern "C" void tts_hip_coalesce_set_wait(int us) { tts::g_wait_us.store(us < 0 ? 0 : us); }

@@ -166,6 +166,9 @@ struct Item {
     // ATTN
     const tts_tensor *q = nullptr, *k = nullptr, *v = nullptr, *mask = nullptr, *out = nullptr;
     const tts_tensor * bias = nullptr;  // added to KQ before the softmax (k_attn_bias), [P, n, H]
+    // v is a stand-in for this skipped CONT of a transposed cache view (try_attn): a coalesced step makes each
+    // member's stand-in from the CONT at the same position of that member's graph
+    const tts_tensor * v_cont = nullptr;
     bool stage = false;     // ATTN with a bias: out overlaps an operand; written to be->attn_stage, then copied
     float scale = 1.f;
     // LN
@@ -310,6 +313,10 @@ struct Planner {
     char * hoist_buf = nullptr;  // backend scratch for hoisted products whose own memory is still in use (try_gemv)
     size_t hoist_cap = 0, hoist_used = 0;
     int hoist_live = -1;  // the last node position whose COPY item still reads the hoist buffer
+    // planning a coalesced step (be->bat): no hoisting through backend scratch (one column; such a product stays at
+    // its own position as its own GEMV item, hoist_buf is null), and a single token GET_ROWS becomes a one-term
+    // EMBED item (one launch over the members' own index tensors instead of a node run per member)
+    bool co = false;
     size_t lstm_cap = 0, lstm_used = 0;
 
     static bool read_after(const tts_tensor * t) { return (t->flags & (TTS_FLAG_OUTPUT | TTS_FLAG_PERSIST)) != 0; }
@@ -383,6 +390,9 @@ struct Planner {
         if (mask & TTS_FUSE_EMBED)  // roots first: a chain is claimed whole by its last ADD
             for (int i = n - 1; i >= 0; --i)
                 if (act[i] == 0 && nodes[i]->op == TTS_OP_ADD) try_embed(i);
+        if (co && (mask & TTS_FUSE_EMBED))
+            for (int i = 0; i < n; ++i)
+                if (act[i] == 0 && nodes[i]->op == TTS_OP_GET_ROWS) try_embed_one(i);
         tmark("embed");
         for (int i = 0; i < n; ++i) {
             if (act[i] != 0) continue;
@@ -864,7 +874,8 @@ struct Planner {
             if (!(mask & TTS_FUSE_GROUP)) break;
             // a product of the same activation in another weight type (a Q6_K v_proj between Q4_K k_proj and q_proj)
             // ends the group: a later member hoisted over it and its KV store lands on memory they still use, i.e. in
-            // backend scratch, which a coalesced step cannot take.  Each type's products run as their own items.
+            // backend scratch, which a coalesced step does not use (it plans such a product at its own position, so
+            // the two plans would differ in more than that one item).  Each type's products run as their own items.
             if (j > i && act[j] == 0 && mm->op == TTS_OP_MUL_MAT && mm->src[1] == x && is_gemv(mm) && mm->src[0]->type != a0->type) break;
             if (std::find(skips.begin(), skips.end(), j) != skips.end()) {  // a member's KV store: absorbed
                 ++j;
@@ -1859,6 +1870,23 @@ struct Planner {
         act[i] = add_item(std::move(it));
     }
 
+    // A coalesced step's token embedding (Orpheus' single GET_ROWS, model.cpp:282): one row of a 2-D table into a
+    // contiguous F32 vector, as a one-term EMBED item -- k_embed_sum's first term is k_get_rows' value, unrounded.
+    void try_embed_one(int i) {
+        const tts_tensor * G = nodes[i];
+        const tts_tensor *W = G->src[0], *ix = G->src[1];
+        if (!W || !ix || ix->type != TTS_TYPE_I32 || G->type != TTS_TYPE_F32 || !contiguous(G)) return;
+        if (G->ne[1] * G->ne[2] * G->ne[3] != 1 || ix->ne[0] * ix->ne[1] * ix->ne[2] * ix->ne[3] != 1) return;
+        if (W->ne[2] * W->ne[3] != 1 || G->ne[0] != W->ne[0] || overlap(G, W) || overlap(G, ix)) return;
+        // the forms co_prepare has tables for: a weight leaf indexed by an input leaf (anything else stays a node)
+        if (W->op != TTS_OP_NONE || W->view_src || ix->op != TTS_OP_NONE || ix->view_src || !(ix->flags & TTS_FLAG_INPUT)) return;
+        Item it;
+        it.kind = Item::EMBED;
+        it.dst = G;
+        it.terms = {G};
+        act[i] = add_item(std::move(it));
+    }
+
     // orpheus_build_kv_store (Orpheus model.cpp:194-228): `repeat` CPYs of one source into strided
     // cache views, K's and V's interleaved.  All CPY consumers of the source run as one pass when
     // nothing but CPYs and views sits between the first and the last (the destinations are disjoint
@@ -1977,6 +2005,7 @@ struct Planner {
         const tts_tensor * V = KQV->src[1];
         const tts_tensor * K = Ka;
         int skip_k = -1, skip_q = -1, skip_v = -1;
+        const tts_tensor * v_cont = nullptr;
         // V = cont_{3,4}d(transpose(view of a [dims, positions] cache)) (Orpheus model.cpp:265-272): read the
         // transposed cache in place, V'(p, d, h, b) = T(p, d + hd*h, b); the per-step transpose copy disappears
         // folds only read tensors whose storage outlives the graph (caches, weights, inputs): an arena
@@ -2001,6 +2030,7 @@ struct Planner {
                 d.view_src = T->view_src ? T->view_src : const_cast<tts_tensor *>(T);
                 for (int k = 0; k < TTS_MAX_SRC; ++k) d.src[k] = nullptr;
                 skip_v = index[V];
+                v_cont = V;
                 V = &d;
             }
         }
@@ -2091,6 +2121,7 @@ struct Planner {
         it.q = Q;
         it.k = K;
         it.v = V;
+        it.v_cont = v_cont;
         it.mask = mask;
         it.bias = bias;
         it.stage = stage;
@@ -2575,6 +2606,26 @@ static int run_node_coalesced(tts_hip_backend * be, const tts_tensor * n) {
         }
         if (per_slice) return launch_op(be, &t);
     }
+    if (n->op == TTS_OP_CPY) {  // into each member's own cache rows: one launch over the members (co_prepare-checked)
+        const auto f = bc.ntab.find(n);
+        if (f != bc.ntab.end()) {
+            tts_tensor x = *n->src[0];
+            x.data = bc.win(x.data);
+            launch_cpy_multi_co(be, &x, &n, 1, bc.N, bc.stride(n->src[0]->data), f->second.doff);
+            return 0;
+        }
+    }
+    if (n->op == TTS_OP_ROPE) {  // each member at its own positions (an input): one launch over the members (co_prepare-checked)
+        const auto f = bc.ntab.find(n);
+        if (f != bc.ntab.end()) {
+            tts_tensor d = *n, x = *n->src[0];
+            d.data = bc.win(n->data);
+            x.data = bc.win(x.data);
+            const tts_tensor * dp = &d;
+            launch_rope_multi_co(be, n, &x, &dp, 1, bc.N, bc.stride(n->src[0]->data), f->second.doff, f->second.poff);
+            return 0;
+        }
+    }
     BatchCtx * keep = be->bat;
     be->bat = nullptr;  // member k's own node, run as in an uncoalesced step
     int st = 0;
@@ -2583,7 +2634,9 @@ static int run_node_coalesced(tts_hip_backend * be, const tts_tensor * n) {
         const tts_tensor * m = co_member(bc, x, k);
         return m ? m->data : nullptr;
     };
+    if (co_debug()) fprintf(stderr, "coalesce: node %s (%s) runs once per member\n", n->name, tts_op_name(n->op));
     for (int k = 0; k < bc.N && st == 0; ++k) {
+        be->co_node_runs++;
         t = *n;
         t.data = addr(n, k);
         for (int i = 0; i < TTS_MAX_SRC; ++i) {
@@ -2653,6 +2706,14 @@ static int run_item(tts_hip_backend * be, const Item & it, const std::vector<Ite
             launch_adain_snake(be, it.adain);
             return 0;
         case Item::MCPY:
+            if (be->bat) {  // every member's source (its executor copy) into its own cache rows: tab->doff (co_prepare-checked)
+                tts_tensor x = *it.x;
+                x.data = be->bat->win(x.data);
+                const int64_t xms = be->bat->stride(it.x->data);
+                if (it.rope) launch_rope_multi_co(be, it.rope, &x, it.terms.data(), (int)it.terms.size(), be->bat->N, xms, tab->doff, tab->poff);
+                else launch_cpy_multi_co(be, &x, it.terms.data(), (int)it.terms.size(), be->bat->N, xms, tab->doff);
+                return 0;
+            }
             if (it.rope) launch_rope_multi(be, it.rope, it.x, it.terms.data(), (int)it.terms.size());
             else launch_cpy_multi(be, it.x, it.terms.data(), (int)it.terms.size());
             return 0;
@@ -2735,7 +2796,7 @@ static bool co_per_slice(const BatchCtx & bc, const tts_tensor * n) {
 //    own tensor (src, dst, bytes triples in `tab` at *scatter, *n_scatter of them).
 static bool co_prepare(tts_hip_backend * be, Planner & pl, tts_tensor * const * nodes, int n_nodes,
                        std::vector<std::tuple<const void *, const void *, size_t>> & shared, std::vector<int64_t> & tab,
-                       std::vector<std::array<int64_t, 5>> & offs, int64_t * scatter, int * n_scatter) {
+                       std::vector<std::array<int64_t, 7>> & offs, int64_t * scatter, int * n_scatter) {
     BatchCtx & bc = *be->bat;
     CoMap & cm = *(CoMap *)bc.comap;
     const int N = bc.N;
@@ -2779,8 +2840,76 @@ static bool co_prepare(tts_hip_backend * be, Planner & pl, tts_tensor * const * 
         }
         return true;
     };
+    // A member's own F32 rows written by the batched KV store (an MCPY destination view): inside that member's cache
+    // tensor (the view's root), 4-byte aligned, of member 0's shape and strides -- checked here, on the host, for
+    // every member and destination, before any table reaches a kernel; o: where its float offsets from member 0's go
+    auto store_rows = [&](const tts_tensor * D, int64_t o) {
+        if (D->type != TTS_TYPE_F32 || D->nb[0] != 4) return false;
+        for (int k = 0; k < N; ++k) {
+            const tts_tensor * m = cm.member(bc, D, k);
+            const tts_tensor * root = mem_root(m);
+            if (!m || !m->data || !root || !root->data || root == m || !owned_mem(m) || input_mem(m) || bc.stride(m->data)) return false;
+            int64_t ne[4], nb[4];
+            for (int d = 0; d < 4; ++d) {
+                if (m->ne[d] != D->ne[d] || m->nb[d] != D->nb[d]) return false;
+                ne[d] = m->ne[d], nb[d] = (int64_t)m->nb[d];
+            }
+            const int64_t off = (int64_t)((const char *)m->data - (const char *)root->data);
+            if (!tts_hip_coalesce_store_ok(off, ne, nb, (int64_t)tbytes(root))) return false;
+            const int64_t d = (int64_t)((const char *)m->data - (const char *)D->data);
+            if (d % 4) return false;
+            tab[o + k] = d / 4;
+        }
+        return true;
+    };
+    // a ROPE whose positions are each member's own input (and whose frequency factors, if any, are model data): the
+    // batched kernel's form; rope_tables then fills the members' position offsets
+    auto rope_form = [&](const tts_tensor * r) {
+        const tts_tensor *pos = r->src[1], *ff = r->src[2];
+        return pos && pos->type == TTS_TYPE_I32 && pos->nb[0] == 4 && input_mem(pos) &&
+               (!ff || (owned_mem(ff) && !input_mem(ff) && !bc.stride(ff->data)));
+    };
+    auto rope_tables = [&](const tts_tensor * r, int64_t & po) {
+        if (!equal_all(r->src[1]) || !share(r->src[2])) return false;
+        po = alloc(N);
+        return offsets(r->src[1], po, 4);
+    };
+    // a ROPE node over intermediates (r: the node or a NODE item's stand-in): launched once over the members, each
+    // writing its executor copy.  false: refuse the group; a node without the form runs once per member as before
+    auto rope_node = [&](const tts_tensor * r) {
+        const tts_tensor * x = r->src[0];
+        if (!x || r->type != TTS_TYPE_F32 || x->type != TTS_TYPE_F32 || r->ne[3] != 1 || !same_ne(r, x) || !inter(r) || !inter(x) ||
+            (bc.stride(r->data) & 3) || !rope_form(r))
+            return true;
+        ItemTab t;
+        int64_t po = -1;
+        if (!rope_tables(r, po)) return false;
+        const int64_t o = alloc(N);
+        for (int k = 0; k < N; ++k) tab[o + k] = k * (bc.stride(r->data) / 4);
+        t.doff = (const int64_t *)(intptr_t)(o + 1);  // offset + 1 until uploaded
+        t.poff = (const int64_t *)(intptr_t)(po + 1);
+        bc.ntab[r] = t;
+        return true;
+    };
+    // a CPY node from an intermediate into member-owned F32 rows (a KV-store copy the planner left on its own: the
+    // Q4_K_M-style mix's K copies, with the Q6_K V product between them): one batched copy, destinations checked as
+    // an MCPY item's.  false: refuse the group; a node without the form runs once per member as before
+    auto cpy_node = [&](const tts_tensor * c) {
+        const tts_tensor * x = c->src[0];
+        if (!x || c->type != TTS_TYPE_F32 || x->type != TTS_TYPE_F32 || c->nb[0] != 4 || nel(c) != nel(x) || !inter(x) || !owned_mem(c) ||
+            input_mem(c) || bc.stride(c->data) || !mem_root(c) || mem_root(c) == c)
+            return true;
+        if (!equal_all(x)) return false;
+        const int64_t o = alloc(N);
+        if (!store_rows(c, o)) return false;
+        ItemTab t;
+        t.doff = (const int64_t *)(intptr_t)(o + 1);  // offset + 1 until uploaded
+        bc.ntab[c] = t;
+        return true;
+    };
+    bc.ntab.clear();
     bc.tabs.assign(pl.items.size(), ItemTab{});
-    offs.assign(pl.items.size(), std::array<int64_t, 5>{-1, -1, -1, -1, -1});
+    offs.assign(pl.items.size(), std::array<int64_t, 7>{-1, -1, -1, -1, -1, -1, -1});
     std::vector<std::array<int64_t, EMBED_MAX_TERMS>> ioffs(pl.items.size());
     for (auto & r : ioffs) r.fill(-1);
     for (int i = 0; i < n_nodes; ++i) {
@@ -2795,6 +2924,8 @@ static bool co_prepare(tts_hip_backend * be, Planner & pl, tts_tensor * const * 
             if (co_per_slice(bc, nd))
                 for (int s2 = 0; s2 < TTS_MAX_SRC; ++s2)
                     if (nd->src[s2] && owned_mem(nd->src[s2]) && !share(nd->src[s2])) CO_NO();
+            if (nd->op == TTS_OP_ROPE && !rope_node(nd)) CO_NO();
+            if (nd->op == TTS_OP_CPY && !cpy_node(nd)) CO_NO();
             continue;
         }
         Item & it = pl.items[a - 1];
@@ -2802,7 +2933,10 @@ static bool co_prepare(tts_hip_backend * be, Planner & pl, tts_tensor * const * 
         auto & of = offs[a - 1];
         switch (it.kind) {
             case Item::GEMV: {
-                if (it.epi == EPI_SWIGLU || it.epi == EPI_SILU_MUL) CO_NO();
+                // EPI_SWIGLU (gate and up into one target) and EPI_SILU_MUL (it.res: the stored gate product) are per
+                // output element: with the target (and the gate product) an intermediate at the member stride, column k
+                // of the launch reads and writes member k's copies (ycs / rcs, run_gemv_item); checked below like any
+                // other target and residual
                 const tts_tensor * x = it.mms[0]->src[1];
                 if (nel(x) != x->ne[0]) CO_NO();  // one column per member
                 const tts_tensor * xt = it.ln ? it.lnx : it.xsrc ? it.xsrc : x;
@@ -2814,7 +2948,7 @@ static bool co_prepare(tts_hip_backend * be, Planner & pl, tts_tensor * const * 
                 for (size_t k = 0; k < it.mms.size(); ++k) {
                     if (!equal_all(it.mms[k]) || !share(it.mms[k]->src[0])) CO_NO();
                     const GemvTarget & t = it.tgt[k];
-                    if (!t.yt) CO_NO();  // backend scratch (a hoisted product): no per-member form
+                    if (!t.yt) CO_NO();  // backend scratch: a plan made for a coalesced step hoists nothing through it (Planner::co)
                     if (!owned_mem(t.yt)) {
                         if (!bc.stride(t.y)) CO_NO();
                         continue;
@@ -2842,9 +2976,30 @@ static bool co_prepare(tts_hip_backend * be, Planner & pl, tts_tensor * const * 
                 int * pseq = (int *)&tab[of[3]];
                 int pmax = 0;
                 bool ragged = false;
+                // V as try_attn's stand-in for a skipped CONT of a transposed cache view (Orpheus): member k's stand-in is
+                // made the same way from the CONT at that position of member k's graph
+                std::vector<tts_tensor> vder;
+                if (it.v_cont) {
+                    vder.resize(N);
+                    for (int k = 0; k < N; ++k) {
+                        const tts_tensor * Vk = cm.member(bc, it.v_cont, k);
+                        const tts_tensor * T = Vk ? Vk->src[0] : nullptr;
+                        if (!T || !T->data || T->ne[3] != 1 || T->type != TTS_TYPE_F32 || Vk->type != TTS_TYPE_F32 || Vk->ne[0] != T->ne[0] ||
+                            Vk->ne[1] * Vk->ne[2] != T->ne[1] || Vk->ne[3] != T->ne[2] || !owned_mem(T))
+                            CO_NO();
+                        tts_tensor & d = vder[k];
+                        d = *Vk;
+                        d.data = T->data;
+                        d.nb[0] = T->nb[0];
+                        d.nb[1] = T->nb[1];
+                        d.nb[2] = T->nb[1] * Vk->ne[1];
+                        d.nb[3] = T->nb[2];
+                    }
+                    if (vder[0].data != it.v->data) CO_NO();
+                }
                 for (int k = 0; k < N; ++k) {
                     const tts_tensor * mk = cm.member(bc, it.k, k);
-                    const tts_tensor * mv = cm.member(bc, it.v, k);
+                    const tts_tensor * mv = it.v_cont ? &vder[k] : cm.member(bc, it.v, k);
                     if (!mk || !mv || mk->ne[0] != it.k->ne[0] || mk->ne[2] != it.k->ne[2] || mk->ne[3] != 1 || mv->ne[1] != it.v->ne[1] ||
                         mv->ne[2] != it.v->ne[2] || mv->ne[3] != 1 || mv->ne[0] != mk->ne[1] || mk->nb[1] != it.k->nb[1] ||
                         mk->nb[2] != it.k->nb[2] || mv->nb[1] != it.v->nb[1] || mv->nb[2] != it.v->nb[2] || mk->nb[0] != it.k->nb[0] ||
@@ -2869,7 +3024,13 @@ static bool co_prepare(tts_hip_backend * be, Planner & pl, tts_tensor * const * 
                     }
                     if (bc.stride(kv->data)) CO_NO();
                     of[1 + w] = alloc(N);
-                    if (!offsets(kv, of[1 + w], 16)) CO_NO();  // 16-B aligned: the kernels' vector loads
+                    if (w && it.v_cont) {
+                        for (int k = 0; k < N; ++k) {
+                            const int64_t d = (int64_t)((const char *)vder[k].data - (const char *)kv->data);
+                            if (d % 16) CO_NO();
+                            tab[of[1 + w] + k] = d / 16;
+                        }
+                    } else if (!offsets(kv, of[1 + w], 16)) CO_NO();  // 16-B aligned: the kernels' vector loads
                     for (int k = 0; k < N; ++k) tab[of[1 + w] + k] *= 16;
                 }
                 if (it.mask) {
@@ -2914,9 +3075,23 @@ static bool co_prepare(tts_hip_backend * be, Planner & pl, tts_tensor * const * 
                 if (co_per_slice(bc, &it.node))
                     for (int s2 = 0; s2 < TTS_MAX_SRC; ++s2)
                         if (it.node.src[s2] && owned_mem(it.node.src[s2]) && !share(it.node.src[s2])) CO_NO();
+                if (it.node.op == TTS_OP_ROPE && !rope_node(&it.node)) CO_NO();
                 break;
             }
-            default: CO_NO();  // LSTM / SNAKE / CONV / ADAIN / MCPY / RINT / COPY: vocoder and prefill items
+            case Item::MCPY: {
+                // the KV store (Orpheus' rope(K) and its repeat copies): every member's source is its executor copy, its
+                // destinations its own cache rows at its own position ([destination][N] float offsets from member 0's)
+                const int nd = (int)it.terms.size();
+                if (nd < 1 || nd > 4 || it.x->type != TTS_TYPE_F32 || it.x->ne[3] != 1 || !inter(it.x) || !equal_all(it.x)) CO_NO();
+                if (it.rope && (!rope_form(it.rope) || !same_ne(it.rope, it.x) || !rope_tables(it.rope, of[6]))) CO_NO();
+                of[5] = alloc((size_t)nd * N);
+                for (int d = 0; d < nd; ++d)
+                    if (nel(it.terms[d]) != nel(it.x) || !store_rows(it.terms[d], of[5] + (int64_t)d * N)) CO_NO();
+                break;
+            }
+            // LSTM / SNAKE / CONV / ADAIN / RINT: vocoder and prefill items; COPY: a product hoisted through backend
+            // scratch, which a plan made for a coalesced step never forms (Planner::co)
+            default: CO_NO();
         }
     }
     // the output intermediates back to every member: the last node and nodes marked output
@@ -3220,7 +3395,8 @@ static void plan_setup(Planner & pl, const tts_hip_backend * be) {
     pl.vec_cap = be->vec_scratch ? (1u << 18) : 0;
     pl.conv_stage = be->conv_stage;
     pl.conv_stage_cap = be->conv_stage_floats;
-    pl.hoist_buf = (char *)be->hoist;
+    pl.co = be->bat != nullptr;
+    pl.hoist_buf = pl.co ? nullptr : (char *)be->hoist;
     pl.hoist_cap = be->hoist_size;
 }
 
@@ -3252,7 +3428,7 @@ int graph_compute_launches(tts_hip_backend_t be, tts_tensor * const * nodes, int
         bc.comap = &cm;
         std::vector<std::tuple<const void *, const void *, size_t>> shared;
         std::vector<int64_t> tab;
-        std::vector<std::array<int64_t, 5>> offs;
+        std::vector<std::array<int64_t, 7>> offs;
         if (!co_prepare(be, pl, nodes, n_nodes, shared, tab, offs, &sc_off, &n_sc)) {
             bc.comap = nullptr;
             return TTS_STATUS_UNSUPPORTED;
@@ -3284,8 +3460,14 @@ int graph_compute_launches(tts_hip_backend_t be, tts_tensor * const * nodes, int
             tb.voff = of[2] >= 0 ? be->co_tab + of[2] : nullptr;
             tb.pseq = of[3] >= 0 ? (const int *)(be->co_tab + of[3]) : nullptr;
             tb.moff = of[4] >= 0 ? be->co_tab + of[4] : nullptr;
+            tb.doff = of[5] >= 0 ? be->co_tab + of[5] : nullptr;
+            tb.poff = of[6] >= 0 ? be->co_tab + of[6] : nullptr;
             for (auto & io : tb.ioff)
                 if (io) io = be->co_tab + ((intptr_t)io - 1);
+        }
+        for (auto & nt : bc.ntab) {
+            if (nt.second.doff) nt.second.doff = be->co_tab + ((intptr_t)nt.second.doff - 1);
+            if (nt.second.poff) nt.second.poff = be->co_tab + ((intptr_t)nt.second.poff - 1);
         }
     }
     // long-context attention items in launch order: each one's K/V is prefetched into MALL on the

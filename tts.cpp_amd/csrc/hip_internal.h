@@ -481,6 +481,10 @@ struct ItemTab {
     const int * pseq = nullptr;                      // ATTN: key count per member
     int pmax = 0;
     const int64_t * ioff[EMBED_MAX_TERMS] = {};      // EMBED: index offsets per member (elements)
+    // MCPY / a ROPE node: member k's destination d at dst[d] + doff[d * N + k] floats (its own cache rows, or its
+    // executor copy of an intermediate); member k's rope positions at pos + poff[k] elements (its own input)
+    const int64_t * doff = nullptr;
+    const int64_t * poff = nullptr;
 };
 struct BatchCtx {
     int N = 0;
@@ -494,6 +498,8 @@ struct BatchCtx {
     bool ragged = false;        // (co_prepare) the members' KV lengths differ
     bool differs = false;       // refused because a member's read-only data differs (not for lack of a batched form)
     std::vector<ItemTab> tabs;  // per plan item (graph_exec.hip)
+    // per ROPE node launched once over the members (a plain node, or a NODE item's stand-in): its doff / poff
+    std::unordered_map<const tts_tensor *, ItemTab> ntab;
     void * comap = nullptr;     // graph_exec.hip: member 0's tensors -> graph positions (member k's counterparts)
     const BatchCls * find(const void * p) const {
         const char * c = (const char *)p;
@@ -683,6 +689,7 @@ struct tts_hip_backend {
     int64_t * co_tab = nullptr;  // device copy of a coalesced plan's per-item tables (ItemTab)
     size_t co_tab_bytes = 0;
     int64_t co_prep_ns = 0;      // host time of co_prepare + the tables' upload (coalesced steps)
+    int64_t co_node_runs = 0;    // node runs made once per member inside coalesced steps (run_node_coalesced)
     bool co_member = true;  // TTS_HIP_OPT_COALESCE: this backend's graph_compute calls may join a coalesced step
     // read-back of a coalesced step's outputs: the executor copies this member's output tensors into
     // rb_host (pinned) in the step's own stream order, so tts_hip_tensor_get of such a range is served
@@ -750,6 +757,12 @@ void launch_repeat_interleave1(tts_hip_backend * be, const tts_tensor * dst, con
 void launch_copy_bytes(tts_hip_backend * be, void * dst, const void * src, size_t bytes);
 void launch_cpy_multi(tts_hip_backend * be, const tts_tensor * src, const tts_tensor * const * dsts, int nd);
 void launch_rope_multi(tts_hip_backend * be, const tts_tensor * rope, const tts_tensor * src, const tts_tensor * const * dsts, int nd);
+// the same two passes over the N members of a coalesced step (the member is a grid dimension): member k's source
+// at src + k * xms bytes, its destination d at dsts[d] + doff[d * N + k] floats, its rope positions at pos + poff[k]
+void launch_cpy_multi_co(tts_hip_backend * be, const tts_tensor * src, const tts_tensor * const * dsts, int nd, int N, int64_t xms,
+                         const int64_t * doff);
+void launch_rope_multi_co(tts_hip_backend * be, const tts_tensor * rope, const tts_tensor * src, const tts_tensor * const * dsts, int nd,
+                          int N, int64_t xms, const int64_t * doff, const int64_t * poff);
 void launch_greedy_step(tts_hip_backend * be, const float * logits, int B, int NH, int V, int step, int bos, int eos, int32_t * eos_seen,
                         int32_t * hist, int32_t * next);
 int launch_sample_step(tts_hip_backend * be, const float * logits, int B, int NH, int V, const tts_sampling * c, int64_t call,

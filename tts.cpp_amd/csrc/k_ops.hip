@@ -490,13 +490,14 @@ __global__ __launch_bounds__(256) void k_sum_rows(TD dst, TD a) {
 // ---- ROPE (NORM / NEOX, optional freq factors; theta by repeated multiply as ggml_rope_cache_init) ----
 // dst: one or more destinations of the source's shape (the planner's rope + repeat-copy item writes
 // every repeat copy of the rotated K directly)
-__global__ void k_rope(CpyMulti m, TD a, const int32_t * pos, const float * ff, int n_dims, int neox, float theta_scale,
-                       float freq_scale, float attn_factor) {
+// (one row (i1, i2, i3) of the source per 64-thread workgroup: the body of k_rope and of k_rope_co, so that a
+// coalesced step rotates with exactly the arithmetic of a step run alone)
+static __device__ __forceinline__ void rope_row(const CpyMulti & m, const TD & a, int64_t i1, int64_t i2, int64_t i3, int64_t p,
+                                                const float * ff, int n_dims, int neox, float theta_scale, float freq_scale,
+                                                float attn_factor) {
     auto td_store_all = [&](int64_t j0, int64_t i1, int64_t i2, int64_t i3, float v) {
         for (int d = 0; d < m.nd; ++d) td_store(m.dst[d], j0, i1, i2, i3, v);
     };
-    const int64_t i1 = blockIdx.x, i2 = blockIdx.y, i3 = blockIdx.z;
-    const int64_t p = pos[i2];
     for (int64_t i0 = 2 * threadIdx.x; i0 < a.ne[0]; i0 += 2 * blockDim.x) {
         if (i0 < n_dims) {
             float theta = (float)p;
@@ -521,6 +522,45 @@ __global__ void k_rope(CpyMulti m, TD a, const int32_t * pos, const float * ff, 
             td_store_all(i0, i1, i2, i3, x0);
             if (i0 + 1 < a.ne[0]) td_store_all(i0 + 1, i1, i2, i3, x1);
         }
+    }
+}
+
+__global__ void k_rope(CpyMulti m, TD a, const int32_t * pos, const float * ff, int n_dims, int neox, float theta_scale,
+                       float freq_scale, float attn_factor) {
+    const int64_t i1 = blockIdx.x, i2 = blockIdx.y, i3 = blockIdx.z;
+    rope_row(m, a, i1, i2, i3, pos[i2], ff, n_dims, neox, theta_scale, freq_scale, attn_factor);
+}
+
+// ---- the KV store and the rope of a coalesced step (coalesce.hip): N one-prompt members, the member a grid
+// dimension.  Member k's source is its executor copy (a.data + k * xms), its destinations lie doff[d * N + k]
+// floats from member 0's (each member's own cache rows at its own position, host-checked against that member's
+// cache tensor before the tables are uploaded: co_prepare), its positions poff[k] elements from member 0's.
+// Sources of one dim-3 slice (one token per member); plain vector stores, nothing shared between workgroups. ----
+struct CoMulti {
+    const int64_t * doff;
+    const int64_t * poff;
+    int64_t xms;
+    int N;
+};
+static __device__ __forceinline__ void co_member_views(CpyMulti & m, TD & a, const CoMulti & co, int k) {
+    a.data += (int64_t)k * co.xms;
+    for (int d = 0; d < m.nd; ++d) m.dst[d].data += 4 * co.doff[(int64_t)d * co.N + k];
+}
+__global__ void k_rope_co(CpyMulti m, CoMulti co, TD a, const int32_t * pos, const float * ff, int n_dims, int neox,
+                          float theta_scale, float freq_scale, float attn_factor) {
+    const int k = blockIdx.z;
+    const int64_t i1 = blockIdx.x, i2 = blockIdx.y;
+    co_member_views(m, a, co, k);
+    rope_row(m, a, i1, i2, 0, pos[co.poff[k] + i2], ff, n_dims, neox, theta_scale, freq_scale, attn_factor);
+}
+__global__ void k_cpy_multi_co(CpyMulti m, CoMulti co, TD src, int64_t n) {
+    co_member_views(m, src, co, blockIdx.y);
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+        int64_t a0, a1, a2, a3, b0, b1, b2, b3;
+        unravel(k, src.ne, a0, a1, a2, a3);
+        const float v = td_load(src, a0, a1, a2, a3);
+        unravel(k, m.dst[0].ne, b0, b1, b2, b3);
+        for (int i = 0; i < m.nd; ++i) td_store(m.dst[i], b0, b1, b2, b3, v);
     }
 }
 
@@ -611,6 +651,36 @@ void launch_rope_multi(tts_hip_backend * be, const tts_tensor * rope, const tts_
     dim3 grid((unsigned)src->ne[1], (unsigned)src->ne[2], (unsigned)src->ne[3]);
     hipLaunchKernelGGL(k_rope, grid, dim3(64), 0, be->stream, m, make_td(src), (const int32_t *)rope->src[1]->data,
                        ff ? (const float *)ff->data : nullptr, n_dims, (mode & 2) ? 1 : 0, theta_scale, freq_scale, attn_factor);
+    TTS_HIP_CHECK(hipGetLastError());
+}
+
+void launch_rope_multi_co(tts_hip_backend * be, const tts_tensor * rope, const tts_tensor * src, const tts_tensor * const * dsts, int nd,
+                          int N, int64_t xms, const int64_t * doff, const int64_t * poff) {
+    CpyMulti m{};
+    m.nd = nd;
+    for (int i = 0; i < nd; ++i) m.dst[i] = make_td(dsts[i]);
+    const CoMulti co{doff, poff, xms, N};
+    const int n_dims = rope->op_params[1];
+    const int mode = rope->op_params[2];
+    const float freq_base = op_f(rope, 5), freq_scale = op_f(rope, 6), attn_factor = op_f(rope, 8);
+    const float theta_scale = powf(freq_base, -2.0f / n_dims);
+    const tts_tensor * ff = rope->src[2];
+    dim3 grid((unsigned)src->ne[1], (unsigned)src->ne[2], (unsigned)N);  // (co_prepare: src->ne[3] == 1)
+    hipLaunchKernelGGL(k_rope_co, grid, dim3(64), 0, be->stream, m, co, make_td(src), (const int32_t *)rope->src[1]->data,
+                       ff ? (const float *)ff->data : nullptr, n_dims, (mode & 2) ? 1 : 0, theta_scale, freq_scale, attn_factor);
+    TTS_HIP_CHECK(hipGetLastError());
+}
+
+void launch_cpy_multi_co(tts_hip_backend * be, const tts_tensor * src, const tts_tensor * const * dsts, int nd, int N, int64_t xms,
+                         const int64_t * doff) {
+    CpyMulti m{};
+    m.nd = nd;
+    for (int i = 0; i < nd; ++i) m.dst[i] = make_td(dsts[i]);
+    const CoMulti co{doff, nullptr, xms, N};
+    const int64_t n = nel(src);
+    if (n == 0) return;
+    const int64_t g = (n + 255) / 256;
+    hipLaunchKernelGGL(k_cpy_multi_co, dim3((unsigned)(g < 4096 ? g : 4096), (unsigned)N), dim3(256), 0, be->stream, m, co, make_td(src), n);
     TTS_HIP_CHECK(hipGetLastError());
 }
 

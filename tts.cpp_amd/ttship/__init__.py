@@ -357,6 +357,7 @@ def lib():
         "tts_hip_gemv_res": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, vp, vp, i64, i64, i64, i32]),
         "tts_hip_counters": (ctypes.c_int, [vp, ctypes.POINTER(i64), ctypes.c_int]),
         "tts_hip_coalesce_stats": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(i64), ctypes.c_int]),
+        "tts_hip_coalesce_store_ok": (ctypes.c_int, [i64, ctypes.POINTER(i64), ctypes.POINTER(i64), i64]),
         "tts_hip_coalesce_set_wait": (None, [ctypes.c_int]),
         "tts_hip_coalesce_enable": (ctypes.c_int, [ctypes.c_int]),
         "tts_hip_test_hook": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
@@ -775,11 +776,18 @@ class _Runner:
 
 def coalesce_stats(device=0):
     """Step-coalescer counters of `device` (tts_hip_coalesce_stats)."""
-    out = (ctypes.c_int64 * 11)()
-    n = lib().tts_hip_coalesce_stats(device, out, 11)
+    out = (ctypes.c_int64 * 12)()
+    n = lib().tts_hip_coalesce_stats(device, out, 12)
     keys = ("launches", "member_steps", "alone", "refused", "max_group", "wait_us", "ragged_launches", "exec_us", "layout_us",
-            "plan_us", "tables_us")
+            "plan_us", "tables_us", "member_node_runs")
     return {keys[i]: int(out[i]) for i in range(max(n, 0))}
+
+
+def coalesce_store_ok(off_bytes, ne, nb, cache_bytes):
+    """The coalescer's host bounds check of one batched KV-store destination (tts_hip_coalesce_store_ok): an F32
+    view of shape ne[4] and byte strides nb[4], off_bytes into a cache tensor of cache_bytes, lies inside it."""
+    a, b = (ctypes.c_int64 * 4)(*[int(v) for v in ne]), (ctypes.c_int64 * 4)(*[int(v) for v in nb])
+    return bool(lib().tts_hip_coalesce_store_ok(int(off_bytes), a, b, int(cache_bytes)))
 
 
 def coalesce_set_wait(us):
